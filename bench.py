@@ -1,12 +1,20 @@
 #!/usr/bin/env python3
 """Benchmark of the classification hot path on MI355X (BASELINE.json metric).
 
-    python bench.py                              # 1 GPU: configs[1] timed; configs[2] and [4] reported under `workloads`
+    python bench.py                              # 1 GPU: configs[1] timed, the headline line only
+    python bench.py --full                       # ... and everything else below: configs[2] and [4] under `workloads`, checks
     python bench.py --workload cfg3|cfg5|se|f64  # another workload as the timed one
     python bench.py --gpus N --steps K --warmup W   # N > 1: starts its own N ranks (one per GPU, RCCL)
     python bench.py --gpus N --sharded-input     # configs[3] as ONE input cut into N read blocks with halo (strong scaling)
+    python bench.py --dump-outputs DIR           # also writes what the last timed step computed, DIR/<name>.npy (float64)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W            # ... or is started as a rank
+
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the line: `value`,
+`ms_per_step` and the classify kernel's `roofline` from the HIP events inside the timed region.  Everything that takes
+work of its own -- the check against the C oracle, the median step, the per-kernel pass and `roofline_step`, the
+on-box copy ceilings, the CPU baselines, `e2e`, the other workloads, the library's RCCL all-reduce, the full record
+file -- runs with --full only (the --no-* options below then leave parts of it out).
 
 One step = one pass of the hot path over one batch of synthetic input that is already resident in HBM, through
 ONE C-ABI call (xm_classify_compact_dev; --cigar_scores: xm_classify_compact_cigar_packed_dev): K1 classify + count
@@ -22,7 +30,7 @@ Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (classify): 
 kernel's mean duration, measured with HIP events on the launch stream inside the timed region; `traffic` = HBM bytes
 per launch from the committed rocprofv3 --pmc passes, printed only while the kernel sources still hash to what they
 were measured on (tools/kernel_hash.py).  `roofline_step` is SURVEY 8d's whole-step figure: 38 B per pair / the sum of
-the kernels' mean durations (and / ms_per_step).  `workloads` (default run): configs[2] and configs[4] timed the same
+the kernels' mean durations (and / ms_per_step).  `workloads` (--full): configs[2] and configs[4] timed the same
 way in the same process.  `cpu_baseline` is the oracle's Python restatement of the reference's whole CPU path (parse +
 classify + write) on SAM text, timed on one host core at N = 1 on a bounded sample.  `e2e` holds the transfer-inclusive
 rates SURVEY 8d asks for beside it (never `value`) with their own ceilings: host columns in / bin lists out over PCIe
@@ -47,6 +55,8 @@ HBM_PEAK_GBPS = 8000.0                 # MI355X HBM3E spec peak (guides/MI355X_M
 BYTES_PER_PAIR_CLASSIFY = 33.0         # algorithmic: 2 mates x 4 int32 scores in + 1 category byte out
 BYTES_PER_PAIR_COMPACT = 5.0           # 1 category byte in + one u32 pair index out
 EXTRA_WORKLOADS = (("configs[2]", "cfg3"), ("configs[4]", "cfg5"))     # timed after the default run, reported under `workloads`
+DUMP_SAMPLE = 1 << 19                  # --dump-outputs: longer outputs are written as this many seeded positions (4 MB each)
+DUMP_SEED = 20240611
 
 
 def parse_args():
@@ -67,8 +77,14 @@ def parse_args():
     ap.add_argument("--singletons-pct", type=float, default=0.0,
                     help="cfg2/cfg5: this percentage of the reads are singletons (no mate), so the mates are not strictly "
                          "interleaved and the scatter takes its general path")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region: oracle check, median step, per-kernel pass, copy ceilings, CPU baselines, e2e, "
+                         "the other workloads, the library's all-reduce and the full record file (a plain run: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; outputs longer than %d "
+                         "entries as a fixed, seeded sample of them)" % DUMP_SAMPLE)
     ap.add_argument("--no-extra-workloads", action="store_true",
-                    help="default run only: skip timing configs[2] and configs[4] after the timed region (the `workloads` key)")
+                    help="--full, default run only: skip timing configs[2] and configs[4] after the timed region (the `workloads` key)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the transfer-inclusive side measurements")
@@ -517,6 +533,35 @@ class Workload(object):
         self.step_counts.zero_()
         self.step_no = 0
 
+    def outputs(self):
+        """What the last step handed its caller, as device tensors by name: the form's own outputs, cut to the lengths its
+        offsets / list sizes give, unsigned words widened to int64.  bins4 appears as `bins` (one entry per record)."""
+        import torch
+        u32 = lambda t: t.to(torch.int64) & 0xFFFFFFFF                    # noqa: E731 -- int32 storage of uint32 indices
+        out = {}
+        if self.runs:
+            out["runs16"] = self.runs16.to(torch.int64) & 0xFFFF
+            out["gran_counts"] = self.gran_counts.to(torch.int64) & 0xFFFF
+            out["n_out"] = self.n_out
+        elif self.place:
+            n_out = self.n_out.cpu().tolist()
+            for b, lst in enumerate(self.lists):
+                out["list%d" % b] = u32(lst[:n_out[b]])
+            out["n_out"] = self.n_out
+        else:
+            out["idx"] = u32(self.idx[:int(self.off[7].item())])
+            out["off"] = self.off
+        if not self.runs:
+            if self.category_bytes:
+                out["code"] = self.code[:self.n]
+            else:                                    # record r = nibble r & 1 of byte r >> 1 (_ffi.unpack_bins4)
+                b = self.bins4[:(self.n + 1) // 2]
+                out["bins"] = torch.stack([b & 7, (b >> 4) & 7], dim=1).reshape(-1)[:self.n]
+        out["counts"] = self.counts
+        if self.range_flag is not None:
+            out["range_flag"] = self.range_flag
+        return out
+
     def host_columns(self):
         import numpy as np
         hc = {k: v.cpu().numpy() for k, v in self.cols.items()}
@@ -604,9 +649,30 @@ def singleton_unit_flags(n_records, p_single, seed):
     return flags
 
 
-def time_steps(ctx, wl, steps, warmup, fence, finish=None):
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: every output as out_dir/<name>.npy in float64 (the values are integers below 2**53, so exact).
+    One longer than DUMP_SAMPLE entries is written at DUMP_SAMPLE positions drawn with DUMP_SEED (sorted, repeats
+    dropped): the same positions for the same length, so two builds compare output for output.  -> bytes written"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, t in outputs.items():
+        t = t.reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            at = np.unique(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.index_select(0, torch.from_numpy(at).to(t.device))
+        a = t.cpu().numpy().astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += a.nbytes
+    assert written <= 64 << 20, written
+    return written
+
+
+def time_steps(ctx, wl, steps, warmup, fence, finish=None, each_kernel=True):
     """`warmup` untimed steps, then exactly `steps` steps (+ finish()) between two fences, HIP events around the classify
-    kernel only; then a diagnostic pass with every kernel bracketed.  -> (elapsed s, classify timing, all-kernel timing)"""
+    kernel only; then (each_kernel) a diagnostic pass with every kernel bracketed, kernel_pass().  -> (elapsed s,
+    classify timing, all-kernel timing or None)"""
     for _ in range(warmup):
         wl.step()
     if finish is not None:
@@ -626,15 +692,22 @@ def time_steps(ctx, wl, steps, warmup, fence, finish=None):
     fence()
     elapsed = time.perf_counter() - t0
     timing = ctx.timing_read()
-    # diagnostic pass outside the timed region: every kernel bracketed (the event pairs cost stream time)
+    ctx.timing_enable(False)
+    return elapsed, timing, kernel_pass(ctx, wl, steps, fence) if each_kernel else None
+
+
+def kernel_pass(ctx, wl, steps, fence):
+    """Diagnostic pass outside the timed region: min(steps, 20) further steps, every kernel bracketed (the event pairs
+    cost stream time).  -> all-kernel timing"""
     ctx.timing_select(None)
+    ctx.timing_enable(True)
     ctx.timing_reset()
     for _ in range(min(steps, 20)):
         wl.step()
     fence()
     timing_all = ctx.timing_read()
     ctx.timing_enable(False)
-    return elapsed, timing, timing_all
+    return timing_all
 
 
 def median_step_ms(wl, steps=20):
@@ -701,28 +774,32 @@ def _r(x, digits=5):
 def compact_line(full):
     """The ONE JSON line rank 0 prints: numbers only, well under 2 000 characters, so that a record which keeps the
     line's tail still holds every workload.  The sentences (what each number is) live in profiles/README.md; the full
-    record of the run is written next to it (`full_record`)."""
-    roof, step = full["roofline"], full["roofline_step"]
+    record of the run is written next to it (`full_record`).  A plain run (no --full) has no `roofline_step`,
+    `kernel_ms`, median or side measurements: those keys are left out."""
+    roof, step = full["roofline"], full.get("roofline_step")
     line = {k: full[k] for k in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "scaling", "vs_baseline",
                                  "dtype", "data")}
     line["value"] = _r(full["value"], 6)
     line["ms_per_step"] = _r(full["ms_per_step"])
-    line["ms_per_step_median"] = _r(full.get("ms_per_step_median"))
+    if full.get("ms_per_step_median") is not None:
+        line["ms_per_step_median"] = _r(full["ms_per_step_median"])
     line["config"] = {"workload": full["config"]["workload_short"], "pairs_per_gpu": full["config"]["pairs_per_gpu"],
                       "step": full["config"]["step_short"], "sharding": full["config"]["sharding_short"]}
     line["roofline"] = {"bound": "hbm", "kernel": roof["kernel"].split("<")[0], "achieved": _r(roof["achieved"]), "peak": roof["peak"],
                         "unit": "GB/s", "frac": _r(roof["frac"], 4), "traffic": _r(roof["traffic"]), "kernel_ms": _r(roof["kernel_ms"]),
                         "bytes_per_unit": _r(roof["algorithmic_bytes_per_unit"]), "copy_ceiling_GBps": _r(roof.get("copy_ceiling_GBps"), 4),
                         "memcpy_d2d_GBps": _r(roof.get("memcpy_d2d_GBps"), 4), "frac_of_copy": _r(roof.get("frac_of_copy"), 4)}
-    line["roofline_step"] = {"frac": _r(step["frac"], 4), "frac_by_ms_per_step": _r(step["frac_by_ms_per_step"], 4),
-                             "sum_kernel_ms": _r(step["sum_kernel_ms"]), "bytes_per_unit": _r(step["algorithmic_bytes_per_unit"]),
-                             "traffic": _r(step["traffic"])}
-    line["kernel_ms"] = {k: _r(v, 4) for k, v in full["kernel_ms"].items()}
+    if step is not None:
+        line["roofline_step"] = {"frac": _r(step["frac"], 4), "frac_by_ms_per_step": _r(step["frac_by_ms_per_step"], 4),
+                                 "sum_kernel_ms": _r(step["sum_kernel_ms"]), "bytes_per_unit": _r(step["algorithmic_bytes_per_unit"]),
+                                 "traffic": _r(step["traffic"])}
+    if full.get("kernel_ms") is not None:
+        line["kernel_ms"] = {k: _r(v, 4) for k, v in full["kernel_ms"].items()}
     cb = full.get("cpu_baseline")
     if cb:
         line["cpu_baseline"] = {"value": _r(cb["value"]), "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
                                 "sample": cb["sample_short"]}
-    line["verified_vs_oracle"] = full["verified_vs_oracle"]
+    line["verified_vs_oracle"] = full.get("verified_vs_oracle")
     line["n_ranks_seen"] = full["n_ranks_seen"]
     x = full.get("xm_allreduce_counts")
     if x is not None:
@@ -761,28 +838,32 @@ def compact_line(full):
                        _r((rate(e2e, "sam_text_host_stripper", "read_pairs_per_s") or 0) / 1e6, 4),
                        _r((rate(e2e, "bam_host_decoder", "read_pairs_per_s") or 0) / 1e6, 4),
                        _r(rate(e2e, "inflate", "value") or 0, 4)]
-    line["full_record"] = full.get("full_record")
+    if "full_record" in full:
+        line["full_record"] = full["full_record"]
     return line
 
 
 def rooflines(wl, elapsed, steps, timing, timing_all, unit_name):
-    """The `roofline` (dominant kernel) and `roofline_step` (whole step) objects + per-kernel means of one workload."""
+    """The `roofline` (dominant kernel) and `roofline_step` (whole step) objects + per-kernel means of one workload;
+    without the per-kernel pass (timing_all None) only `roofline`: (roof, None, None)."""
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import kernel_hash
     k_cls = timing["classify"]
     cls_ms = k_cls["ms"] / max(1, k_cls["launches"])
     achieved = wl.bytes_classify * wl.units_per_step / (cls_ms * 1e-3) / 1e9
-    kernels = {k: round(v["ms"] / max(1, v["launches"]), 5) for k, v in timing_all.items() if v["launches"]}
-    sum_ms = sum(kernels.values())
-    step_bytes = (wl.bytes_classify + wl.bytes_compact) * wl.units_per_step
-    step_achieved = step_bytes / (sum_ms * 1e-3) / 1e9
-    ms_per_step = 1e3 * elapsed / steps
     traffic = step_traffic = source = None
     if not (wl.unfused or wl.place or wl.runs or wl.category_bytes or wl.shard or "singletons" in wl.layout):
         traffic, step_traffic, source = kernel_hash.load_traffic(wl.name, wl.n_pairs)
     roof = {"bound": "hbm", "kernel": wl.kernel_name(), "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
             "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": source,
             "algorithmic_bytes_per_unit": wl.bytes_classify, "kernel_ms": cls_ms}
+    if timing_all is None:
+        return roof, None, None
+    kernels = {k: round(v["ms"] / max(1, v["launches"]), 5) for k, v in timing_all.items() if v["launches"]}
+    sum_ms = sum(kernels.values())
+    step_bytes = (wl.bytes_classify + wl.bytes_compact) * wl.units_per_step
+    step_achieved = step_bytes / (sum_ms * 1e-3) / 1e9
+    ms_per_step = 1e3 * elapsed / steps
     step = {"bound": "hbm", "what": "SURVEY 8d: (classify + compact) algorithmic bytes per %s / sum of the kernels' mean durations" % unit_name,
             "algorithmic_bytes_per_unit": wl.bytes_classify + wl.bytes_compact, "sum_kernel_ms": round(sum_ms, 5),
             "achieved": step_achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": step_achieved / HBM_PEAK_GBPS,
@@ -873,8 +954,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    elapsed, timing, timing_all = time_steps(ctx, wl, args.steps, args.warmup, fence, finish)
-    step_median_ms = median_step_ms(wl, 20)
+    elapsed, timing, _ = time_steps(ctx, wl, args.steps, args.warmup, fence, finish, each_kernel=False)
+    if args.dump_outputs and rank == 0:                       # before anything else runs a step on the same buffers
+        outs = wl.outputs()
+        outs["job_counts"] = job_counts
+        dump_outputs(outs, args.dump_outputs)
+    timing_all = step_median_ms = None
+    if args.full:
+        timing_all = kernel_pass(ctx, wl, args.steps, fence)
+        step_median_ms = median_step_ms(wl, 20)
     job_total = int(job_counts.sum().item())
     job_final = job_counts.clone()
     last_counts = wl.counts.clone()
@@ -886,7 +974,7 @@ def main():
 
     # parity of what was just timed (rank-local): against the C oracle on the same columns
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         from tests import helpers as H
         if rank == 0:
             H.c_oracle()                       # (re)builds oracle/libxm_oracle.so if stale: once, not in N ranks at a time
@@ -901,14 +989,15 @@ def main():
     if rank == 0:
         unit_name = "read" if args.workload == "se" else "read-pair"
         roof, roof_step, kernels = rooflines(wl, elapsed, args.steps, timing, timing_all, unit_name)
-        try:        # an on-box streaming-copy ceiling beside the spec peak, same footprint as the classify kernel
-            roof["memcpy_d2d_GBps"] = copy_ceiling_gbps(dev, wl.bytes_classify * wl.units_per_step)
-            probe = stream_ceiling_gbps(ctx, wl)
-            roof["copy_ceiling_GBps"] = probe if probe is not None else roof["memcpy_d2d_GBps"]
-            roof["copy_ceiling_kind"] = "xm_stream_probe_dev" if probe is not None else "hipMemcpyDtoD"
-            roof["frac_of_copy"] = roof["achieved"] / roof["copy_ceiling_GBps"]
-        except Exception as e:                                   # noqa: BLE001
-            roof["copy_ceiling_GBps"], roof["frac_of_copy"], roof["copy_ceiling_error"] = None, None, "%s: %s" % (type(e).__name__, e)
+        if args.full:
+            try:    # an on-box streaming-copy ceiling beside the spec peak, same footprint as the classify kernel
+                roof["memcpy_d2d_GBps"] = copy_ceiling_gbps(dev, wl.bytes_classify * wl.units_per_step)
+                probe = stream_ceiling_gbps(ctx, wl)
+                roof["copy_ceiling_GBps"] = probe if probe is not None else roof["memcpy_d2d_GBps"]
+                roof["copy_ceiling_kind"] = "xm_stream_probe_dev" if probe is not None else "hipMemcpyDtoD"
+                roof["frac_of_copy"] = roof["achieved"] / roof["copy_ceiling_GBps"]
+            except Exception as e:                               # noqa: BLE001
+                roof["copy_ceiling_GBps"], roof["frac_of_copy"], roof["copy_ceiling_error"] = None, None, "%s: %s" % (type(e).__name__, e)
         if args.sharded_input:
             job = ("ONE %d-pair input (%d seeded parts end to end) cut into %d read blocks of ~%d pairs with a one-record halo%s"
                    % (args.strong_total, Workload.PARTS, world, n_pairs,
@@ -945,14 +1034,14 @@ def main():
             "xm_allreduce_counts": None,
         }
         host_cols = getattr(wl, "host_cols", None)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_python()
             if host_cols is not None and args.workload in ("cfg2", "cfg5") and not args.sharded_input:
                 m = min(n_pairs, 5_000_000)
                 sub = {k: np.ascontiguousarray(v[:2 * m]) for k, v in host_cols.items() if k != "unit_bits"}
                 sub["unit_bits"] = np.ascontiguousarray(host_cols["unit_bits"][:(2 * m + 63) // 64])
                 line["cpu_baseline_c"] = cpu_baseline_c(sub, m)
-        if world == 1 and not args.no_e2e and args.workload == "cfg2" and not args.sharded_input and not args.singletons_pct:
+        if world == 1 and args.full and not args.no_e2e and args.workload == "cfg2" and not args.sharded_input and not args.singletons_pct:
             e2e = {"note": "transfer-inclusive rates beside `value` (which is HBM-resident); measured after the timed region"}
             try:
                 hc = host_cols if host_cols is not None else wl.host_columns()
@@ -1013,16 +1102,16 @@ def main():
                 e2e["host_ceilings"] = {"error": "%s: %s" % (type(e).__name__, e)}
             line["e2e"] = e2e
 
-    # The other BASELINE configs, timed the same way in this process after the headline run (default invocation only):
+    # The other BASELINE configs, timed the same way in this process after the headline run (--full, default configuration):
     # configs[2] --cigar_scores and configs[4] HISAT ZS + conservative (one GPU), and -- at every N -- configs[3]'s input:
     # 400 M pairs as ONE input cut into N read blocks with the halo record (strong scaling), so that one scaling run of
-    # the default command yields both curves of SURVEY 8d.  `value`/`config` stay configs[1].
-    plain_default = (args.workload == "cfg2" and not args.no_extra_workloads and not args.sharded_input
-                     and not args.singletons_pct and not args.strong_total and args.pairs == 50_000_000
-                     and not wl.unfused and not wl.place and not wl.runs and os.environ.get("XM_BENCH_CATEGORY_BYTES") != "1")
-    default_run = world == 1 and plain_default
+    # the --full command yields both curves of SURVEY 8d.  `value`/`config` stay configs[1].
+    default_config = (args.full and args.workload == "cfg2" and not args.no_extra_workloads and not args.sharded_input
+                      and not args.singletons_pct and not args.strong_total and args.pairs == 50_000_000
+                      and not wl.unfused and not wl.place and not wl.runs and os.environ.get("XM_BENCH_CATEGORY_BYTES") != "1")
+    default_run = world == 1 and default_config
     extra = {}
-    if plain_default:
+    if default_config:
         del wl
         torch.cuda.empty_cache()
     if default_run:
@@ -1105,7 +1194,7 @@ def main():
             torch.cuda.empty_cache()
         except Exception as e:                                   # noqa: BLE001
             extra["graph"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if plain_default:
+    if default_config:
         try:
             total = 400_000_000 - 400_000_000 % (Workload.PARTS * 32)
             w3 = Workload("cfg2", ctx, dev, total // world, rank, None, 10, 0.0, (total, world), form="place")
@@ -1160,14 +1249,14 @@ def main():
             ctx.comm_destroy()
             return out
 
-    if not rehearsal or os.environ.get("XM_BENCH_FAKE_HANG") == "1":
+    if args.full and (not rehearsal or os.environ.get("XM_BENCH_FAKE_HANG") == "1"):
         try:
             outcome = run_with_watchdog(library_allreduce, watchdog_s, line, "xm_allreduce_counts", rank)
         except Exception as e:                                   # noqa: BLE001 -- reported, not raised
             outcome = {"error": "%s: %s" % (type(e).__name__, e)}
         if rank == 0:
             line["xm_allreduce_counts"] = outcome
-    if rank == 0:
+    if rank == 0 and args.full:
         # the full record goes to a file, the printed line stays short (numbers only)
         path = os.environ.get("XM_BENCH_FULL_JSON") or os.path.join(REPO, "gpurun_out", "bench_full_%dgpu_%s.json" % (world, args.workload))
         try:
@@ -1177,6 +1266,7 @@ def main():
             line["full_record"] = os.path.relpath(path, REPO)
         except OSError:
             line["full_record"] = None
+    if rank == 0:
         out = compact_line(line)
         if os.environ.get("XM_BENCH_VERBOSE") == "1":
             out = line

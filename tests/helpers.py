@@ -1,5 +1,6 @@
 """Shared test plumbing: golden vectors, the oracle (Python + C), SAM inputs of golden cases."""
 import ctypes
+import gzip
 import json
 import os
 import subprocess
@@ -20,7 +21,7 @@ MODES = {"se": 0, "pe": 1, "pe_conservative": 2}
 
 
 def golden(name):
-    with open(os.path.join(GOLDEN, name), "rt") as fh:
+    with (gzip.open if name.endswith(".gz") else open)(os.path.join(GOLDEN, name), "rt") as fh:
         return json.load(fh)
 
 

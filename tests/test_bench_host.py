@@ -131,3 +131,42 @@ def test_printed_line_stays_short_enough_for_a_truncating_record():
     full["xm_allreduce_counts"] = {"error": "watchdog: " + "h" * 500}
     line = json.dumps(bench.compact_line(full), separators=(",", ":"))
     assert len(line) < 1900 and json.loads(line)["workloads"]["cfg3"][0] is None
+
+
+def test_plain_line_leaves_out_what_only_the_full_run_measures():
+    """A plain run (no --full) has no per-kernel pass, median, side measurements or full record: the line carries the
+    headline keys and the classify kernel's roofline, and no nulls in place of what was not measured."""
+    import bench
+    roof = {"bound": "hbm", "kernel": "classify_kernel<int32, paired, counts>", "achieved": 5669.8, "peak": 8000.0, "unit": "GB/s",
+            "frac": 0.70872, "traffic": None, "traffic_source": None, "algorithmic_bytes_per_unit": 33.0, "kernel_ms": 0.29102}
+    full = {"metric": "read-pairs/sec classified", "value": 139591123456.7, "unit": "read-pairs/s", "n_gpus": 1, "n_ranks_seen": 1,
+            "steps": 50, "warmup": 5, "ms_per_step": 0.358191, "ms_per_step_median": None, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "int32", "data": "synthetic",
+            "config": {"workload_short": "w", "pairs_per_gpu": 50_000_000, "step_short": "s", "sharding_short": "weak"},
+            "roofline": roof, "roofline_step": None, "kernel_ms": None, "verified_vs_oracle": None, "xm_allreduce_counts": None}
+    rec = json.loads(json.dumps(bench.compact_line(full), separators=(",", ":")))
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(rec)
+    assert rec["ms_per_step"] == 0.35819 and rec["roofline"]["frac"] == 0.7087
+    assert not {"ms_per_step_median", "roofline_step", "kernel_ms", "cpu_baseline", "e2e", "workloads", "full_record"} & set(rec)
+
+
+def test_dumped_outputs_are_float64_and_sampled_at_the_same_positions(tmp_path):
+    """--dump-outputs: every output as <name>.npy in float64; one longer than DUMP_SAMPLE entries at positions that
+    depend on its length only, so two runs (two builds) compare output for output."""
+    import numpy as np
+    import torch
+    import bench
+    n = 3 * bench.DUMP_SAMPLE
+    outs = {"idx": torch.arange(n, dtype=torch.int64) * 3, "off": torch.tensor([0, 5, 9], dtype=torch.int64),
+            "bins": (torch.arange(n) % 8).to(torch.uint8)}
+    written = bench.dump_outputs(outs, str(tmp_path / "a"))
+    bench.dump_outputs({k: v.clone() for k, v in outs.items()}, str(tmp_path / "b"))
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in outs}
+    assert sorted(os.listdir(tmp_path / "a")) == ["bins.npy", "idx.npy", "off.npy"]
+    assert all(v.dtype == np.float64 for v in got.values()) and written == sum(v.nbytes for v in got.values())
+    assert got["off"].tolist() == [0.0, 5.0, 9.0]                           # short: whole
+    at = got["idx"] / 3                                                     # long: sorted distinct positions, <= DUMP_SAMPLE
+    assert 0.8 * bench.DUMP_SAMPLE < at.shape[0] <= bench.DUMP_SAMPLE and (np.diff(at) > 0).all()
+    assert np.array_equal(got["bins"], at % 8)
+    for k in outs:
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / (k + ".npy")))

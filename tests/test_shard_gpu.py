@@ -145,7 +145,7 @@ def test_bench_starts_its_own_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     proc = subprocess.run([sys.executable, os.path.join(H.REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                           "--pairs", "1000000", "--no-cpu-baseline", "--no-e2e"], env=env, capture_output=True, text=True,
+                           "--pairs", "1000000", "--full", "--no-cpu-baseline", "--no-e2e"], env=env, capture_output=True, text=True,
                           timeout=600)
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [l for l in proc.stdout.splitlines() if l.strip()]

@@ -14,7 +14,7 @@ cd /tmp && export TMPDIR=/tmp
 for W in $WORKLOADS; do
   # "runs": the segmented-lists form of configs[1] (xm_classify_runs_dev, one launch) -- bench.py --workload cfg2 with XM_BENCH_RUNS=1
   if [ "$W" = runs ]; then export XM_BENCH_RUNS=1; BW=cfg2; else unset XM_BENCH_RUNS; BW=$W; fi
-  ARGS="--workload $BW --steps 20 --warmup 3 --no-cpu-baseline --no-e2e --no-verify --no-extra-workloads"
+  ARGS="--workload $BW --steps 20 --warmup 3 --full --no-cpu-baseline --no-e2e --no-verify --no-extra-workloads"
   echo "== $W: kernel trace"; date
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/stats_$W" -o "$W" --output-format csv -- python3 "$ROOT/bench.py" $ARGS > "$OUT/bench_trace_$W.json" 2> "$OUT/trace_$W.err" || { echo "trace $W failed"; tail -5 "$OUT/trace_$W.err"; exit 1; }
   for C in FETCH_SIZE WRITE_SIZE; do

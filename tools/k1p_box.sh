@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 ARGS="--workload cfg3 --no-cpu-baseline --no-e2e --no-verify --no-extra-workloads"
 echo "== box $(hostname) $(date -u +%FT%TZ)"
 (rocm-smi --showclocks 2>/dev/null | grep -i "sclk\|mclk\|fclk" | head -4) || true
-python3 "$ROOT/bench.py" $ARGS --steps 30 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -3 "$OUT/bench.err"; exit 1; }
+python3 "$ROOT/bench.py" $ARGS --steps 30 --warmup 5 --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -3 "$OUT/bench.err"; exit 1; }
 python3 - "$OUT/bench.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -21,7 +21,9 @@ Vectors:
   G8  100 k-pair text twins of configs 1, 2, 3, 5: counts, digests of the six outputs, summary
   G9  the command line as a child process: stdout, stderr, exit code, output files
   G10 the companion tool's command line as a child process
+  G11 the rows of tests/test_oracle_vs_reference.py: its property test's draws, the companion tool's helpers
 """
+import gzip
 import hashlib
 import io
 import itertools
@@ -626,6 +628,56 @@ def g10():
     return {"cases": cases}
 
 
+# ------------------------------------------------------------------ G11
+def g11(n_cases=300):
+    """tests/test_oracle_vs_reference.py's rows: `cases` = n_cases draws of its strategies (derandomized: the same draws
+    every time) through the reference's three loops, as G7 records them; `mappability` = the companion tool's text and
+    small-list functions on odd inputs."""
+    import importlib
+    from hypothesis import HealthCheck, given, settings, strategies as st
+    from tests.test_host_fuzz import sam_pair
+    draws = []
+
+    @settings(max_examples=n_cases, derandomize=True, database=None, deadline=None, suppress_health_check=list(HealthCheck))
+    @given(texts=sam_pair(), mode=st.sampled_from(["se", "pe", "pe_conservative"]),
+           func=st.sampled_from(["get_cigarbased_AS_tag", "get_tag", "get_tag_with_ZS_as_XS"]),
+           m=st.sampled_from([NEG, 0.0, -12.5, 3.0, float("inf")]), skip=st.booleans())
+    def draw(texts, mode, func, m, skip):
+        draws.append((texts, mode, func, m, skip))
+    draw()
+    cases = []
+    for (t1, t2), mode, func, m, skip in draws:
+        outs = {name: io.StringIO() for name in BIN_ARGS}
+        loop = {"se": ref.main_single_end, "pe": ref.main_paired_end, "pe_conservative": ref.conservative_main_paired_end}[mode]
+        err, counts = None, None
+        try:
+            got = loop(ref.getReadPairs(io.StringIO(t1, newline=None), io.StringIO(t2, newline=None), skip_repeated_reads=skip),
+                       min_score=m, tag_func=getattr(ref, func), **outs)
+            counts = {("|".join(key) if isinstance(key, tuple) else key): v for key, v in sorted(got.items())}
+        except Exception as exc:
+            err = type(exc).__name__
+        cases.append({"text": [t1, t2], "mode": mode, "tag_func": func, "min_score": num(m), "skip_repeated": skip,
+                      "error": err, "counts": counts, "outputs": {name: outs[name].getvalue() for name in BIN_ARGS}})
+
+    mp = importlib.import_module("xenomapper.mappability")
+    dec = "fixedStep\tchrom=%s\tstart=1\tstep=1\n"
+    wiggles = ["", dec % "a" + "1\n0.5\n" + dec % "b" + dec % "c=d" + "2\n", "3\n4\n", dec % "a",
+               dec % "a" + "1\n" + dec % "a" + "7\n8\n", dec % "z" + "1e-3\n" + dec % "y" + dec % "x"]
+    rows = {"wiggle": [], "fasta": [], "lists": []}
+    for text in wiggles:
+        a = mp.Mappability(chromosome_sizes={})
+        a.from_wiggle(io.StringIO(text))
+        # as [key, value] pairs: a track read before any declaration is keyed None, which a JSON object cannot hold
+        rows["wiggle"].append({"text": text, "tracks": [[k, v] for k, v in a.items()],
+                               "chromosome_sizes": [[k, v] for k, v in a.chromosome_sizes.items()]})
+    for text in ["", "junk\n>a desc\nAC\nGT\n>\nTT\n>b\n\n>c\nA\n", ">x\n", "no header\n", ">>double\nAA\n  >  sp\nCC\n"]:
+        rows["fasta"].append({"text": text, "records": [list(r) for r in mp.parse_fasta(io.StringIO(text))]})
+    for values in ([1, 2, 3, 10, 0, 0, 5] * 5, [0.1, 0.25, 7.0], [3]):
+        rows["lists"].append({"values": values, "smoothed": {str(w): mp.smoothed_list(values, w) for w in (10, 2, 1)},
+                              "normalised": mp.normalised_list(values)})
+    return {"cases": cases, "mappability": rows}
+
+
 def header_golden():
     """process_headers on the PE fixtures (tests/test_xenomapper.py:29-54): full texts."""
     data_dir = os.path.join(REF_ROOT, "xenomapper", "tests", "data")
@@ -641,11 +693,15 @@ def main():
     payload = {"g1_mapping_state.json": g1(), "g2_tag_parsers.json": g2(), "g3_end_to_end.json": g3(),
                "g4_headers.json": header_golden(), "g5_errors.json": g5(), "g6_mappability.json": g6(),
                "g7_random_corpus.json": g7(), "g8_large_runs.json": g8(),
-               "g9_cli.json": g9(), "g10_mappability_cli.json": g10()}
+               "g9_cli.json": g9(), "g10_mappability_cli.json": g10(), "g11_differential.json.gz": g11()}
     for name, obj in payload.items():
-        with open(os.path.join(GOLDEN, name), "wt") as fh:
-            json.dump(obj, fh, indent=None, separators=(",", ":"), sort_keys=True)
-            fh.write("\n")
+        with open(os.path.join(GOLDEN, name), "wb") as raw:
+            text = json.dumps(obj, indent=None, separators=(",", ":"), sort_keys=True) + "\n"
+            if name.endswith(".gz"):                                   # no time stamp: the same bytes every time
+                with gzip.GzipFile(filename="", mode="wb", fileobj=raw, mtime=0, compresslevel=9) as fh:
+                    fh.write(text.encode())
+            else:
+                raw.write(text.encode())
         print(name, os.path.getsize(os.path.join(GOLDEN, name)), "bytes")
     g3c = payload["g3_end_to_end.json"]["cases"]
     seen = set()
