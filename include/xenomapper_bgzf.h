@@ -156,7 +156,7 @@ typedef struct {
     int32_t  eof;                    /* no block of the file is left behind these                                                */
     uint64_t skip;                   /* the first `skip` inflated bytes of the new blocks are not alignment records (the BAM
                                         header: magic, text, reference list); less than the first block's ISIZE                   */
-    uint64_t uploaded;               /* the first `uploaded` of the comp_len staged bytes went up with xm_bamdev_upload already   */
+    uint64_t uploaded;               /* the first `uploaded` of the comp_len staged bytes were noted by xm_bamdev_upload already */
 } xm_bamdev_input;
 
 int xm_bamdev_create(xm_ctx *ctx, int device_id, xm_bamdev **out);
@@ -164,13 +164,11 @@ int xm_bamdev_destroy(xm_bamdev *b);                          /* while ctx is al
 /* room per slot and file for comp_bytes of compressed input, raw_bytes of inflated window, max_blocks, max_records */
 int xm_bamdev_reserve(xm_bamdev *b, int slot, uint64_t comp_bytes, uint64_t raw_bytes, uint64_t max_blocks, uint64_t max_records);
 uint8_t *xm_bamdev_staging(xm_bamdev *b, int slot, int file);
-/* Send the first `bytes` of a file's staging buffer to the device now, on a stream of the slot's own -- from any thread, while
- * the slot is idle (its last xm_bamdev_run has returned, the next has not begun): the next run, told so in `uploaded`, waits for
- * the copy instead of making it.  A later xm_bamdev_reserve that grows the buffers forgets what was sent. */
+/* The first `bytes` of a file's staging buffer are staged for the next run -- from any thread, while the slot is idle (its last
+ * xm_bamdev_run has returned, the next has not begun).  The inflate launch of xm_bamdev_run reads the staging buffers where they
+ * are -- page-locked, device-mapped host memory -- so nothing is sent: the call only notes the count, and the next run refuses an
+ * `uploaded` larger than it (XM_ERR_INVALID_ARG).  A later xm_bamdev_reserve that grows the buffers forgets the count. */
 int xm_bamdev_upload(xm_bamdev *b, int slot, int file, uint64_t bytes);
-/* (By default the inflate launch of xm_bamdev_run reads the staging buffers where they are -- page-locked, device-mapped host memory --
- * and nothing is uploaded at all: xm_bamdev_upload then only notes the count.  XM_BAMDEV_ZEROCOPY=0 in the environment restores the
- * copy into HBM, ahead of the run or inside it.) */
 /* inflate, find the records, strip, pair.  score_mode: XMS_SCORE_AS_XS, XMS_SCORE_AS_ZS, or XMS_SCORE_CIGAR (get_cigarbased_AS_tag,
  * xenomapper.py:228-256: column "AS" then holds NM -- the FIRST optional field that holds the letters decides, :247-250 -- and
  * xm_bamdev_classify makes the packed CIGAR columns of the records' CIGAR words and runs xm_classify_compact_cigar_packed_dev).

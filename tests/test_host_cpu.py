@@ -18,7 +18,7 @@ def _declared(header):
     return sorted(set(re.findall(r"\b(xm[hs]?_[a-z0-9_]+)\s*\(", text)))
 
 
-def test_hip_library_exports_every_declared_symbol():
+def test_hip_library_exports_every_declared_symbol_and_its_abi_versions():
     from xenomapper_amd import _ffi, build
     build.build_hip()
     names = sorted(_declared("xenomapper_hip.h") + _declared("xenomapper_strip.h") + _declared("xenomapper_bgzf.h"))
@@ -27,7 +27,7 @@ def test_hip_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(L, n), n
     assert sorted(_ffi.EXPORTED) == names
-    assert _ffi.lib().xm_abi_version() == 6 and _ffi.lib().xms_abi_version() == 3
+    assert _ffi.lib().xm_abi_version() == 6 and _ffi.lib().xms_abi_version() == 4
     assert b"gfx950" in _ffi.lib().xm_strerror(-2)
 
 
@@ -370,43 +370,6 @@ def test_small_bins_wait_for_the_extension_running_ahead(tmp_path, monkeypatch):
         state.finish(sink)
     pool.shutdown()
     assert path.read_bytes() == b"@HD\n" + b"x" * (2 << 20) + b"small\n"
-
-
-def test_files_are_extended_in_pieces_towards_the_size_the_run_predicts(tmp_path, monkeypatch):
-    """With the fraction of the input read so far, the file is extended towards content / fraction (+ 2 %), piece by piece (each a
-    job of its own: several files take turns in the pool), never further than AHEAD_MOST past the content; a writer that needs
-    bytes the extension has reached does not wait for the rest; at the end of the input nothing is added; finish() cuts back."""
-    import os
-    from concurrent.futures import ThreadPoolExecutor
-    from xenomapper_amd import xenomapper as xm
-    monkeypatch.setattr(xm, "AHEAD_PIECE", 1 << 20)
-    monkeypatch.setattr(xm, "AHEAD_MOST", 16 << 20)
-    calls, real = [], xm._fallocate
-
-    def counted(fd, off, length):
-        calls.append((off, length))
-        return real(fd, off, length)
-    monkeypatch.setattr(xm, "_fallocate", counted)
-    path = tmp_path / "bin.sam"
-    ahead, pool = {}, ThreadPoolExecutor(max_workers=2)
-    with open(path, "wt") as sink:
-        fake = _FakeParser(2 << 20)
-        assert xm._emit_into_file(fake, True, 0, None, sink, ahead, pool, progress=0.25) is True
-        state = ahead[id(sink)]
-        want = int((2 << 20) / 0.25 * 1.02)
-        assert state.settle(want) == want == os.path.getsize(path)
-        assert calls[0] == (0, 2 << 20) and all(n <= (1 << 20) for _off, n in calls[1:]) and len(calls) >= 7
-        assert xm._emit_into_file(fake, True, 0, None, sink, ahead, pool, progress=0.26) is True      # predicted 16.1 MB: the 8.4 there do
-        n_before = len(calls)
-        assert xm._emit_into_file(fake, True, 0, None, sink, ahead, pool, progress=0.001) is True     # predicted 6 GB: capped
-        assert state.settle((6 << 20) + (16 << 20)) == (6 << 20) + (16 << 20)
-        assert len(calls) > n_before
-        assert xm._emit_into_file(fake, True, 0, None, sink, ahead, pool, progress=1.0) is True       # the end: nothing more ahead
-        size = state.settle()
-        assert size == (6 << 20) + (16 << 20) == os.path.getsize(path)
-        state.finish(sink)
-    pool.shutdown()
-    assert path.read_bytes() == b"x" * (8 << 20)
 
 
 def test_the_writer_keeps_one_long_mapping_per_file_and_survives_a_fill_that_fails(tmp_path, monkeypatch):

@@ -441,7 +441,7 @@ def test_closing_a_stripper_leaves_no_dangling_stream_in_the_context():
 
 
 @pytest.mark.parametrize("mode", ["pe", "pe_conservative", "se"])
-def test_outputs_gathered_on_the_device_equal_the_oracle_and_the_host_writer(tmp_path, monkeypatch, mode):
+def test_device_gathered_outputs_equal_the_oracle_and_the_host_writer(tmp_path, monkeypatch, mode):
     """xm_strip_fetch_bins through the file path (windows of 1 MB: ~25 windows): the six outputs gathered on the device equal the
     oracle's and the host writer's (XENOMAPPER_GPU_SAM_BINS=0) byte for byte, every window took the device route for plain
     tab-separated text -- and with a sprinkling of lines whose fields are separated by mixed white space (the reference re-joins
@@ -452,7 +452,6 @@ def test_outputs_gathered_on_the_device_equal_the_oracle_and_the_host_writer(tmp
     from tests.test_file_fuzz_gpu import oracle_run, SCORERS
     from xenomapper_amd import xenomapper as xm
     monkeypatch.setattr(xm, "FILE_WINDOW_BYTES", 1 << 20)
-    monkeypatch.delenv("XENOMAPPER_SAM_READ_AHEAD", raising=False)    # (the default first, the option below)
     paired = mode != "se"
     for mixed in (0.0, 0.0002):
         t1, t2, _info = H.synth.sam_text_pair(n_pairs=30_000, seed=17, profile="bowtie2", paired=paired, read_len=100, mixed_ws=mixed,
@@ -483,22 +482,6 @@ def test_outputs_gathered_on_the_device_equal_the_oracle_and_the_host_writer(tmp
                 assert prof.get("sam_windows_device_bins", 0) == prof["sam_windows"], prof
             else:
                 assert 0 < prof.get("sam_windows_device_bins", 0) < prof["sam_windows"], prof
-            assert prof.get("sam_windows_read_ahead", 0) == 0
-        # XENOMAPPER_SAM_READ_AHEAD=1: every window's bytes read, and sent over the link, while the window in front is stripped --
-        # behind a gap in the other slot's buffer, the tail of the window in front put into the gap when its walk has said where
-        # it stopped (xm_strip_begin_behind / xm_strip_set_lead: the first `lead` bytes of the buffer are no text).  The same
-        # outputs; most windows go that way (not the first two, not those behind a window the host writer still reads).
-        monkeypatch.setenv("XENOMAPPER_GPU_SAM_BINS", "1")
-        monkeypatch.setenv("XENOMAPPER_SAM_READ_AHEAD", "1")
-        outs = {name: io.StringIO() for name in H.STATES}
-        counts = xm.classify_sam_files(paths[0], paths[1], paired=paired, conservative=mode == "pe_conservative", **outs)
-        prof = dict(xm.LAST_FILE_PROFILE)
-        assert dict(counts) == dict(want_counts) and [outs[name].getvalue() for name in H.STATES] == want_texts
-        if mixed == 0.0:
-            assert prof.get("sam_windows_read_ahead", 0) >= prof["sam_windows"] * 2 // 3, prof
-        else:
-            assert prof.get("sam_windows_read_ahead", 0) > 0, prof
-        monkeypatch.delenv("XENOMAPPER_SAM_READ_AHEAD", raising=False)
 
 
 def test_overlapping_units_outgrow_the_output_stream_and_go_to_the_host_writer(tmp_path, monkeypatch):
@@ -512,7 +495,6 @@ def test_overlapping_units_outgrow_the_output_stream_and_go_to_the_host_writer(t
     from tests.test_file_fuzz_gpu import oracle_run, SCORERS
     from xenomapper_amd import xenomapper as xm
     monkeypatch.setattr(xm, "FILE_WINDOW_BYTES", 1 << 20)
-    monkeypatch.delenv("XENOMAPPER_SAM_READ_AHEAD", raising=False)    # (with it the buffers hold a window and the room in front of it)
     xm.release_buffers()                                             # (the process-wide stripper may have grown in a test before: this one counts on its sizes)
     line = "samename\t%d\tchr1\t%d\t30\t50M\t=\t%d\t0\t" + "ACGT" * 12 + "AC\t" + "F" * 50 + "\tAS:i:-5\tXS:i:-9\n"
     text = "".join(line % (99 if k % 2 == 0 else 147, 100 + k, 300 + k) for k in range(40_000))

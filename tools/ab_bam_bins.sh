@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs ON the GPU box: BAM in -> six outputs with the outputs gathered on the device (xm_bamdev_fetch_bins) against round 5's form
-# (text printed on the device, lines gathered by the host), and the copy kernel's workgroup count (0 = the runtime's blit).
+# (text printed on the device, lines gathered by the host).
 #   tools/ab_bam_bins.sh [copies] > gpurun_out/r6/ab_bam_bins.txt
 COPIES=${1:-48000}
 cd "$(dirname "$0")/.."
@@ -16,11 +16,5 @@ print('%-26s %6.2f M pairs/s  %.3f s | strip %.3f inflate_ms %.0f wait_raw %.3f 
 for EXTRA in "" "--files"; do
   echo "== outputs: ${EXTRA:-/dev/null}"
   one "host gathers (r5)" XENOMAPPER_GPU_BAM_BINS=0
-  one "device bins, wg 64" XENOMAPPER_GPU_BAM_BINS=1 XM_BAMDEV_COPY_WG=64
-  one "device bins, wg 16" XENOMAPPER_GPU_BAM_BINS=1 XM_BAMDEV_COPY_WG=16
-  one "device bins, wg 8" XENOMAPPER_GPU_BAM_BINS=1 XM_BAMDEV_COPY_WG=8
-  one "device bins, wg 4" XENOMAPPER_GPU_BAM_BINS=1 XM_BAMDEV_COPY_WG=4
-  one "device bins, wg 2" XENOMAPPER_GPU_BAM_BINS=1 XM_BAMDEV_COPY_WG=2
-  one "device bins, wg 32" XENOMAPPER_GPU_BAM_BINS=1 XM_BAMDEV_COPY_WG=32
-  one "device bins, blit" XENOMAPPER_GPU_BAM_BINS=1 XM_BAMDEV_COPY_WG=0
+  one "device bins" XENOMAPPER_GPU_BAM_BINS=1
 done

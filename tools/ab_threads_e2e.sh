@@ -1,15 +1,14 @@
 #!/bin/bash
-# Same-box A/B of the SAM file path's thread split (ON the GPU box): writer / parser threads (XENOMAPPER_THREADS) against a reader pool
-# of its own for the staging preads (XENOMAPPER_PREAD_THREADS), 4 M pairs, outputs on /dev/null and on tmpfs files, two rounds.
+# Same-box A/B of the SAM file path's writer / parser threads (ON the GPU box, XENOMAPPER_THREADS), 4 M pairs, outputs on /dev/null and
+# on tmpfs files, two rounds.
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT"
 for round in 1 2; do
-  for combo in "0 0" "8 8" "10 6" "12 8" "16 8" "8 0"; do
-    set -- $combo
+  for threads in 0 8 10 12 16; do
     for out in devnull files; do
       if [ $out = files ]; then EXTRA="--out-dir /dev/shm/xm_ab_out"; mkdir -p /dev/shm/xm_ab_out; else EXTRA=""; fi
-      echo -n "round $round threads $1 readers $2 $out: "
-      XENOMAPPER_THREADS=$1 XENOMAPPER_PREAD_THREADS=$2 timeout -k 10 120 python3 tools/bench_e2e.py --pairs 4000000 $EXTRA 2>/dev/null | tail -1 | python3 -c "
+      echo -n "round $round threads $threads $out: "
+      XENOMAPPER_THREADS=$threads timeout -k 10 120 python3 tools/bench_e2e.py --pairs 4000000 $EXTRA 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 ph=d['phases']

@@ -252,11 +252,12 @@ struct __attribute__((packed, aligned(1))) U32Store { uint32_t v; };
 // bytes: with four bytes per access G2 fetched 11.4 GB and wrote 5.0 GB per window for 0.55 GB of records and 0.9 GB of text (PMC,
 // profiles/r06_bam_pmc.txt).  Hence the long fields -- bases, qualities, names: 3/4 of a line -- move SIXTEEN bytes per access
 // (unaligned dwordx4 on both sides); the short ones are gathered four at a time.
+constexpr uint32_t WIDE_MIN = 16u;               // bytes per access of the long fields' paths
 struct WriteChars {
     uint8_t *o;
     unsigned long long acc = 0;
     uint32_t k = 0;                              // bytes waiting in acc (< 4 between calls)
-    uint32_t wide_min = 16u;                     // A/B: 0xFFFFFFFF switches the 16-byte paths off
+    uint32_t wide_min = WIDE_MIN;                // the 16-byte paths run while this is WIDE_MIN
     __device__ __forceinline__ void word(uint32_t w, uint32_t n_bytes)          // n_bytes <= 4, the bytes above them zero
     {
         acc |= (unsigned long long)w << (8u * k);
@@ -735,9 +736,9 @@ pair_kernel(FileRecs f1, FileRecs f2, uint32_t n_launch, int paired, const uint3
 
 // ---------------------------------------------------------------------------------------------------------------------
 struct PerFile {
-    uint8_t *h_comp = nullptr, *d_comp = nullptr;           // staged compressed bytes (+ XMB_COMP_PAD): d_comp = a half of Slot::d_comp_all
+    uint8_t *h_comp = nullptr;                              // staged compressed bytes (+ XMB_COMP_PAD), read in place by the inflate launch
     uint8_t *d_raw = nullptr, *h_raw = nullptr;             // the inflated window: d_raw = a half of Slot::d_raw_all
-    uint32_t *h_seg = nullptr, *d_seg = nullptr, *d_cnt = nullptr, *d_exit = nullptr, *d_base = nullptr;
+    uint32_t *h_seg = nullptr, *d_cnt = nullptr, *d_exit = nullptr, *d_base = nullptr;
     // what the inflate launch notes per block (slot_of): record starts and the stripper's fields of every record
     // the records a sink takes, packed (xm_bamdev_fetch_wanted): bytes, and per record where it went (NO_RECORD: not taken)
     uint8_t *d_packed = nullptr, *h_packed = nullptr;
@@ -775,16 +776,16 @@ struct Slot {
     uint64_t comp_cap = 0, raw_cap = 0, block_cap = 0, record_cap = 0;
     PerFile pf[2];
     // both files' blocks are inflated by ONE launch (a window of one file is only a third of the blocks the chip can hold):
-    // one compressed buffer and one output buffer, file 1's half behind file 0's; one block table, status and CRC array
-    uint8_t *d_comp_all = nullptr, *d_raw_all = nullptr;
-    uint64_t comp_stride = 0, raw_stride = 0;
+    // one output buffer, file 1's half behind file 0's; one block table, status and CRC array
+    uint8_t *d_raw_all = nullptr;
+    uint64_t raw_stride = 0;
     // the packed-record / text buffers of the two files are halves of ONE allocation each (pf[f].d_packed, pf[f].h_packed):
     // xm_bamdev_fetch_bins prints the six outputs into them as one stream
     uint8_t *d_packed_all = nullptr, *h_packed_all = nullptr;
     uint64_t packed_stride = 0;
     uint32_t *d_usize = nullptr, *d_uplace = nullptr, *d_upart = nullptr;      // per unit: bytes of its lines, where they go (fetch_bins)
-    xm_bgzf_block *h_blocks = nullptr, *d_blocks = nullptr;
-    xm_bgzf_walk *h_walk = nullptr, *d_walk = nullptr;      // per block: where its record chain starts and where its results go
+    xm_bgzf_block *h_blocks = nullptr;
+    xm_bgzf_walk *h_walk = nullptr;                         // per block: where its record chain starts and where its results go
     uint32_t *d_status = nullptr, *h_status = nullptr, *d_crc = nullptr, *h_crc = nullptr, *d_work = nullptr;
     int32_t *d_col[4] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t *d_bits = nullptr;
@@ -801,9 +802,7 @@ struct Slot {
     // beside it.  ev_raw marks its end; whoever reads h_raw waits for it (xm_bamdev_raw_wait; a carried tail: the next run).
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_inflated = nullptr, ev_raw = nullptr;
-    // compressed bytes sent ahead (xm_bamdev_upload, from the thread that reads the next window while this slot is idle)
-    hipStream_t up_stream = nullptr;
-    hipEvent_t ev_up[2] = {nullptr, nullptr};
+    // compressed bytes staged ahead (xm_bamdev_upload, from the thread that reads the next window while this slot is idle)
     uint64_t up_len[2] = {0, 0};
     int last_score_mode = XMS_SCORE_AS_XS;   // of the last run: which columns xm_bamdev_classify reads
     bool raw_issued = false;                 // ev_raw has been recorded at least once (stays true: waiting for a past event costs nothing)
@@ -866,9 +865,9 @@ void free_slot(Slot &sl)
 {
     for (int f = 0; f < 2; ++f) {
         PerFile &q = sl.pf[f];
-        hfree(q.h_comp); q.d_comp = nullptr; q.d_raw = nullptr; hfree(q.h_raw);
+        hfree(q.h_comp); q.d_raw = nullptr; hfree(q.h_raw);
         q.d_packed = nullptr; q.h_packed = nullptr; dfree(q.d_wsize); dfree(q.d_place); hfree(q.h_place); dfree(q.d_part);
-        hfree(q.h_seg); dfree(q.d_seg); dfree(q.d_cnt); dfree(q.d_exit); dfree(q.d_base);
+        hfree(q.h_seg); dfree(q.d_cnt); dfree(q.d_exit); dfree(q.d_base);
         dfree(q.d_s_off); dfree(q.d_s_name_off); dfree(q.d_s_name_len); dfree(q.d_s_a); dfree(q.d_s_x); dfree(q.d_s_flag);
         dfree(q.d_s_ncig); dfree(q.d_s_cig_at); dfree(q.d_ncig); dfree(q.d_cig_at); dfree(q.d_cig_tile); dfree(q.d_cig_ops); dfree(q.d_cig_cnt);
         q.slots_len = 0; q.ops_cap = q.cig_records = q.cig_slots = 0;
@@ -880,9 +879,9 @@ void free_slot(Slot &sl)
         q.refs_set = false;
         q.skip_records = q.skip_cig_records = q.llen_records = 0; q.n_refs = 0;
     }
-    dfree(sl.d_comp_all); dfree(sl.d_raw_all); dfree(sl.d_packed_all); hfree(sl.h_packed_all);
+    dfree(sl.d_raw_all); dfree(sl.d_packed_all); hfree(sl.h_packed_all);
     dfree(sl.d_usize); dfree(sl.d_uplace); dfree(sl.d_upart);
-    hfree(sl.h_blocks); dfree(sl.d_blocks); hfree(sl.h_walk); dfree(sl.d_walk); dfree(sl.d_status); hfree(sl.h_status); dfree(sl.d_crc); hfree(sl.h_crc);
+    hfree(sl.h_blocks); hfree(sl.h_walk); dfree(sl.d_status); hfree(sl.h_status); dfree(sl.d_crc); hfree(sl.h_crc);
     for (int c = 0; c < 4; ++c) dfree(sl.d_col[c]);
     dfree(sl.d_bits); dfree(sl.d_code); dfree(sl.d_bins4); dfree(sl.d_idx);
     hfree(sl.h_code); hfree(sl.h_idx);
@@ -917,16 +916,6 @@ static int ensure_cigar(xm_bamdev *b, Slot &sl)
         }
     }
     return XM_OK;
-}
-
-// The inflate launch reads the compressed blocks where the host staged them -- page-locked memory the device has mapped -- instead of
-// a copy in HBM: every chain keeps one 128-byte piece of its block in flight, 8192 chains hide the link's latency, and the copy
-// that is not made is a shader kernel that does not run beside the inflate launch (host <-> device copies are blit kernels on this
-// pool): 20.4-20.7 against 18.5-19.8 M pairs/s end to end (profiles/r05_bam_device_text.txt).  XM_BAMDEV_ZEROCOPY=0: upload first.
-static bool zero_copy_input()
-{
-    static const bool on = [] { const char *v = getenv("XM_BAMDEV_ZEROCOPY"); return !(v && v[0] == '0'); }();
-    return on;
 }
 
 // skip_repeated_reads: the arrays only the skipping walk needs
@@ -984,8 +973,6 @@ int xm_bamdev_create(xm_ctx *ctx, int device_id, xm_bamdev **out)
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.ev_wait, hipEventBlockingSync | hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.ev_inflated, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.ev_raw, hipEventBlockingSync | hipEventDisableTiming);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&sl.up_stream, hipStreamNonBlocking);
-        for (int f = 0; f < 2 && e == hipSuccess; ++f) e = hipEventCreateWithFlags(&sl.ev_up[f], hipEventDisableTiming);
         if (e == hipSuccess) e = hipMalloc((void **)&sl.d_state, 32 * sizeof(uint32_t));
         if (e == hipSuccess) e = xmpin::host_malloc((void **)&sl.h_state, 32 * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc((void **)&sl.d_off_counts, 72 * sizeof(uint64_t));
@@ -1022,7 +1009,6 @@ int xm_bamdev_destroy(xm_bamdev *b)
             (void)xm_workspace_release(b->ctx, sl.stream);
         }
         if (sl.copy_stream) (void)hipStreamSynchronize(sl.copy_stream);
-        if (sl.up_stream) (void)hipStreamSynchronize(sl.up_stream);
         free_slot(sl);
         dfree(sl.d_state); hfree(sl.h_state); dfree(sl.d_off_counts); hfree(sl.h_off_counts);
         dfree(sl.d_work);
@@ -1033,9 +1019,6 @@ int xm_bamdev_destroy(xm_bamdev *b)
         if (sl.ev_inflated) (void)hipEventDestroy(sl.ev_inflated);
         if (sl.ev_raw) (void)hipEventDestroy(sl.ev_raw);
         if (k == 1 && sl.copy_stream) (void)hipStreamDestroy(sl.copy_stream);       // shared by the slots: once, behind both
-        for (int f = 0; f < 2; ++f)
-            if (sl.ev_up[f]) (void)hipEventDestroy(sl.ev_up[f]);
-        if (sl.up_stream) (void)hipStreamDestroy(sl.up_stream);
         if (sl.stream) (void)hipStreamDestroy(sl.stream);
     }
     delete b;
@@ -1051,18 +1034,12 @@ int xm_bamdev_reserve(xm_bamdev *b, int slot, uint64_t comp_bytes, uint64_t raw_
     Slot &sl = b->slot[slot];
     XMB_HIP(b, hipStreamSynchronize(sl.stream));
     if (sl.raw_issued) XMB_HIP(b, hipEventSynchronize(sl.ev_raw));            // THIS slot's last copy (the copy stream also carries the other slot's)
-    XMB_HIP(b, hipStreamSynchronize(sl.up_stream));
     sl.have_columns = false;
     if (comp_bytes > sl.comp_cap) {
         sl.comp_cap = 0;
-        sl.up_len[0] = sl.up_len[1] = 0;                                     // what was sent ahead went to the old buffer
-        sl.comp_stride = (comp_bytes + XMB_COMP_PAD + 255u) & ~(uint64_t)255;
-        XMB_TRY(dalloc(b, sl.d_comp_all, (size_t)(2 * sl.comp_stride)));
-        XMB_HIP(b, hipMemset(sl.d_comp_all, 0, (size_t)(2 * sl.comp_stride)));
-        for (int f = 0; f < 2; ++f) {
+        sl.up_len[0] = sl.up_len[1] = 0;                                     // what was staged ahead went to the old buffer
+        for (int f = 0; f < 2; ++f)
             XMB_TRY(halloc(b, sl.pf[f].h_comp, (size_t)comp_bytes + XMB_COMP_PAD));      // (+ pad: the inflate launch reads it in place)
-            sl.pf[f].d_comp = sl.d_comp_all + f * sl.comp_stride;
-        }
         sl.comp_cap = comp_bytes;
     }
     if (raw_bytes > sl.raw_cap) {
@@ -1084,14 +1061,14 @@ int xm_bamdev_reserve(xm_bamdev *b, int slot, uint64_t comp_bytes, uint64_t raw_
     if (max_blocks > sl.block_cap) {
         sl.block_cap = 0;
         const size_t nb = (size_t)max_blocks + 2;
-        XMB_TRY(halloc(b, sl.h_blocks, 2 * nb)); XMB_TRY(dalloc(b, sl.d_blocks, 2 * nb));
-        XMB_TRY(halloc(b, sl.h_walk, 2 * nb)); XMB_TRY(dalloc(b, sl.d_walk, 2 * nb));
+        XMB_TRY(halloc(b, sl.h_blocks, 2 * nb));
+        XMB_TRY(halloc(b, sl.h_walk, 2 * nb));
         XMB_TRY(dalloc(b, sl.d_status, 2 * nb)); XMB_TRY(halloc(b, sl.h_status, 2 * nb));
         XMB_TRY(dalloc(b, sl.d_crc, 2 * nb)); XMB_TRY(halloc(b, sl.h_crc, 2 * nb));
         for (int f = 0; f < 2; ++f) {
             PerFile &q = sl.pf[f];
             // segments: the blocks plus the pieces of a carried tail (at most as many again)
-            XMB_TRY(halloc(b, q.h_seg, 2 * nb + 4)); XMB_TRY(dalloc(b, q.d_seg, 2 * nb + 4));
+            XMB_TRY(halloc(b, q.h_seg, 2 * nb + 4));
             XMB_TRY(dalloc(b, q.d_cnt, 2 * nb + 4)); XMB_TRY(dalloc(b, q.d_exit, 2 * nb + 4)); XMB_TRY(dalloc(b, q.d_base, 2 * nb + 4));
         }
         sl.block_cap = max_blocks;
@@ -1159,14 +1136,13 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
     if (skip) XMB_TRY(ensure_skip(b, sl, cigar));
     hipStream_t st = sl.stream;
     static const bool profile = getenv("XM_BAMDEV_PROFILE") != nullptr;
-    const bool zero_copy = zero_copy_input();
-    // The block, walk and segment tables (24 + ~110 bytes a block, 4 bytes a segment) are read by the kernels where the host wrote
-    // them -- page-locked, device-mapped -- instead of being copied up first: a copy of 0.1-2 MB is ONE workgroup of the runtime's
-    // blit pulling 4 KB per round trip of the link, 0.3-2.8 ms each and four of them in front of every inflate launch
-    // (profiles/r06_bam_timeline.txt); a chain's own read of its 134 bytes is one round trip per block.  XM_BAMDEV_ZEROCOPY_TABLES=0: copy.
-    static const bool tables_in_place = [] { const char *v = getenv("XM_BAMDEV_ZEROCOPY_TABLES"); return !(v && v[0] == '0'); }();
-    const xm_bgzf_block *blocks_at = tables_in_place ? sl.h_blocks : sl.d_blocks;
-    const xm_bgzf_walk *walk_at = tables_in_place ? sl.h_walk : sl.d_walk;
+    // The inflate launch reads the compressed blocks where the host staged them -- page-locked memory the device has mapped --
+    // instead of a copy in HBM: every chain keeps one 128-byte piece of its block in flight, 8192 chains hide the link's latency,
+    // and the copy that is not made is a shader kernel that does not run beside the inflate launch (host <-> device copies are blit
+    // kernels on this pool): 20.4-20.7 against 18.5-19.8 M pairs/s end to end (profiles/r05_bam_device_text.txt).  The block, walk
+    // and segment tables (24 + ~110 bytes a block, 4 bytes a segment) are read in place as well: a copy of 0.1-2 MB is ONE workgroup
+    // of the runtime's blit pulling 4 KB per round trip of the link, 0.3-2.8 ms each and four of them in front of every inflate
+    // launch (profiles/r06_bam_timeline.txt); a chain's own read of its 134 bytes is one round trip per block.
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
     double t_staged = 0, t_issued = 0, t_sync1 = 0;
@@ -1178,10 +1154,9 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
     {
         // The OTHER slot's printer (G2 of the window in front) first: beside this window's inflate launch the two take 28 ms + 18 ms
         // where one after the other they take 6 + 17 (the decoder's window reads wait behind the printer's 6.6 GB of traffic: an
-        // issue-bound launch turns latency-bound); profiles/r06_ab_serial_fill.txt.  XM_BAMDEV_SERIAL_FILL=0: side by side.
-        static const bool serial = [] { const char *v = getenv("XM_BAMDEV_SERIAL_FILL"); return !(v && v[0] == '0'); }();
+        // issue-bound launch turns latency-bound); profiles/r06_ab_serial_fill.txt.
         Slot &other = b->slot[slot ^ 1];
-        if (serial && other.fill_issued) XMB_HIP(b, hipStreamWaitEvent(st, other.ev_inflated, 0));
+        if (other.fill_issued) XMB_HIP(b, hipStreamWaitEvent(st, other.ev_inflated, 0));
     }
     XMB_HIP(b, hipEventRecord(sl.ev[0], st));
     for (int f = 0; f < 2; ++f) {
@@ -1247,8 +1222,7 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
                 q.h_seg[n_seg++] = w.start;
             }
             sl.h_walk[n_all + k] = w;
-            if (zero_copy) d.cdata_off += (uint64_t)(reinterpret_cast<uintptr_t>(q.h_comp) - reinterpret_cast<uintptr_t>(sl.pf[0].h_comp));
-            else d.cdata_off += (uint64_t)f * sl.comp_stride;
+            d.cdata_off += (uint64_t)(reinterpret_cast<uintptr_t>(q.h_comp) - reinterpret_cast<uintptr_t>(sl.pf[0].h_comp));
             d.out_off = out_in_file + (uint64_t)f * sl.raw_stride;
             sl.h_blocks[n_all + k] = d;
         }
@@ -1256,23 +1230,15 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
         q.h_summary[8] = n_seg;
         first_block[f] = n_all;
         n_all += x.n_blocks;
-        // the part of the staged bytes that went up ahead of this call (xm_bamdev_upload) is waited for, the rest is sent now
+        // `uploaded` may not claim more than xm_bamdev_upload noted (nothing is sent: the launch reads the staging buffer)
         const uint64_t up = x.uploaded < x.comp_len ? x.uploaded : x.comp_len;
         if (up > sl.up_len[f]) return XM_ERR_INVALID_ARG;
-        if (up && !zero_copy) XMB_HIP(b, hipStreamWaitEvent(st, sl.ev_up[f], 0));
-        if (x.comp_len > up && !zero_copy)
-            XMB_HIP(b, hipMemcpyAsync(q.d_comp + up, q.h_comp + up, (size_t)(x.comp_len - up), hipMemcpyHostToDevice, st));
         sl.up_len[f] = 0;
-        if (!tables_in_place) XMB_HIP(b, hipMemcpyAsync(q.d_seg, q.h_seg, (size_t)(n_seg + 1) * 4, hipMemcpyHostToDevice, st));
     }
     t_staged = since();
     if (n_all) {
-        if (!tables_in_place) {
-            XMB_HIP(b, hipMemcpyAsync(sl.d_blocks, sl.h_blocks, (size_t)n_all * sizeof(xm_bgzf_block), hipMemcpyHostToDevice, st));
-            XMB_HIP(b, hipMemcpyAsync(sl.d_walk, sl.h_walk, (size_t)n_all * sizeof(xm_bgzf_walk), hipMemcpyHostToDevice, st));
-        }
-        int rc = xm_bgzf_inflate_walk_dev(b->ctx, st, zero_copy ? sl.pf[0].h_comp : sl.d_comp_all, blocks_at, n_all, sl.d_raw_all, sl.d_status, sl.d_work, walk_at);
-        if (rc == XM_OK) rc = xm_bgzf_crc32_dev(b->ctx, st, sl.d_raw_all, blocks_at, n_all, sl.d_crc);
+        int rc = xm_bgzf_inflate_walk_dev(b->ctx, st, sl.pf[0].h_comp, sl.h_blocks, n_all, sl.d_raw_all, sl.d_status, sl.d_work, sl.h_walk);
+        if (rc == XM_OK) rc = xm_bgzf_crc32_dev(b->ctx, st, sl.d_raw_all, sl.h_blocks, n_all, sl.d_crc);
         if (rc != XM_OK) return rc;
         XMB_HIP(b, hipMemcpyAsync(sl.h_status, sl.d_status, (size_t)n_all * 4, hipMemcpyDeviceToHost, st));
         XMB_HIP(b, hipMemcpyAsync(sl.h_crc, sl.d_crc, (size_t)n_all * 4, hipMemcpyDeviceToHost, st));
@@ -1282,7 +1248,7 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
     for (int f = 0; f < 2; ++f) {
         PerFile &q = sl.pf[f];
         const uint32_t n_seg = q.h_summary[8];
-        const uint32_t *seg_at = tables_in_place ? q.h_seg : q.d_seg;
+        const uint32_t *seg_at = q.h_seg;
         XMB_HIP(b, hipMemsetAsync(q.d_summary, 0, 8 * sizeof(uint32_t), st));
         if (n_seg) {
             // counts, exits, record starts and fields of the blocks' segments came with the inflate launch; the pieces of the
@@ -1457,13 +1423,7 @@ int xm_bamdev_upload(xm_bamdev *b, int slot, int file, uint64_t bytes)
     if (!b || slot < 0 || slot > 1 || file < 0 || file > 1) return XM_ERR_INVALID_ARG;
     Slot &sl = b->slot[slot];
     if (bytes > sl.comp_cap) return XM_ERR_INVALID_ARG;
-    sl.up_len[file] = 0;
-    if (bytes == 0) return XM_OK;
-    XMB_HIP(b, hipSetDevice(b->device));
-    if (zero_copy_input()) { sl.up_len[file] = bytes; return XM_OK; }       // nothing to send: the inflate launch reads the staging buffer
-    XMB_HIP(b, hipMemcpyAsync(sl.pf[file].d_comp, sl.pf[file].h_comp, (size_t)bytes, hipMemcpyHostToDevice, sl.up_stream));
-    XMB_HIP(b, hipEventRecord(sl.ev_up[file], sl.up_stream));
-    sl.up_len[file] = bytes;
+    sl.up_len[file] = bytes;                                                // nothing to send: the inflate launch reads the staging buffer
     return XM_OK;
 }
 
@@ -1666,21 +1626,12 @@ int xm_bamdev_fetch_bins(xm_bamdev *b, int slot, uint64_t n_records, int paired,
     for (int k = 0; k < 8; ++k) out->bin_off[k] = sl.h_state[16 + k];
     line_fill_kernel<<<((paired ? 2u : 1u) * n_units + 255u) / 256u, 256, 0, st>>>(
         sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, refs[0], refs[1], sl.d_idx, d_off, n_units, n, paired ? 1 : 0, sink_mask,
-        sl.pf[0].d_wsize, sl.pf[1].d_wsize, sl.d_usize, sl.d_uplace, sl.d_packed_all, (uint32_t)out_cap,
-        []() -> uint32_t { static const bool off = [] { const char *v = getenv("XM_BAMDEV_FILL_WIDE"); return v && v[0] == '0'; }(); return off ? 0xFFFFFFFFu : 16u; }());
+        sl.pf[0].d_wsize, sl.pf[1].d_wsize, sl.d_usize, sl.d_uplace, sl.d_packed_all, (uint32_t)out_cap, WIDE_MIN);
     // the stream goes to the host on the copy stream behind the kernels (beside the next window's inflate launch on the other slot)
     XMB_HIP(b, hipEventRecord(sl.ev_inflated, st));
     sl.fill_issued = true;
     XMB_HIP(b, hipStreamWaitEvent(sl.copy_stream, sl.ev_inflated, 0));
-    if (total) {
-        const uint32_t wg = out_copy_workgroups();
-        if (wg == 0u) XMB_HIP(b, hipMemcpyAsync(sl.h_packed_all, sl.d_packed_all, (size_t)total, hipMemcpyDeviceToHost, sl.copy_stream));
-        else {
-            const uint64_t n16 = (total + 15u) / 16u;                       // (the buffers end 64 bytes behind out_cap)
-            out_copy_launch((uint32_t)std::min<uint64_t>(out_copy_waves(wg), (n16 + 63u) / 64u), sl.copy_stream,
-                            reinterpret_cast<const v4u32 *>(sl.d_packed_all), reinterpret_cast<v4u32 *>(sl.h_packed_all), n16);
-        }
-    }
+    out_copy(sl.d_packed_all, sl.h_packed_all, total, sl.copy_stream);      // (the buffers end 64 bytes behind out_cap)
     XMB_HIP(b, hipEventRecord(sl.ev_raw, sl.copy_stream));
     sl.raw_issued = true;
     if (hipGetLastError() != hipSuccess) return XM_ERR_HIP;

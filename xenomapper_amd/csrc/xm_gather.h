@@ -6,7 +6,6 @@
 #include <chrono>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 namespace {
 
@@ -91,26 +90,17 @@ bin_start_kernel(const uint32_t *__restrict__ uplace, const unsigned long long *
 
 // G3: the stream to the host's page-locked buffer (device-mapped), 16 bytes per lane and step, both sides 16-byte aligned.  Its own
 // kernel instead of hipMemcpyAsync, whose shader blit takes whatever share of the chip it likes beside the next window's inflate
-// launch: this one is a fixed, small number of ONE-WAVE workgroups (XM_BAMDEV_COPY_WG of them x 4), each streaming its contiguous
-// share with four pieces per lane in flight.  One wave per workgroup because the inflate launch beside it is persistent and holds
-// every wave slot its LDS allows -- 31 of a CU's 32: a single wave finds the free slot at once, a workgroup of four waits until four
-// chains on one CU have run out of blocks, i.e. for the end of the launch it was meant to run beside.
+// launch: this one is a fixed, small number of ONE-WAVE workgroups, each streaming its contiguous share with four pieces per lane in
+// flight.  One wave per workgroup because the inflate launch beside it is persistent and holds every wave slot its LDS allows -- 31
+// of a CU's 32: a single wave finds the free slot at once, a workgroup of four waits until four chains on one CU have run out of
+// blocks, i.e. for the end of the launch it was meant to run beside.
 typedef uint32_t v4u32 __attribute__((ext_vector_type(4)));
-template <int DEEP>
 __global__ void __launch_bounds__(64)
-out_copy_kernel_t(const v4u32 *__restrict__ src, v4u32 *__restrict__ dst, uint64_t n16)
+out_copy_kernel(const v4u32 *__restrict__ src, v4u32 *__restrict__ dst, uint64_t n16)
 {
     const uint64_t per = (n16 + gridDim.x - 1u) / gridDim.x;
     const uint64_t lo = per * blockIdx.x, hi = lo + per < n16 ? lo + per : n16;
     uint64_t k = lo + threadIdx.x;
-    if (DEEP == 8)
-        for (; k + 448u < hi; k += 512u) {
-            v4u32 r[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) r[q] = __builtin_nontemporal_load(src + k + 64u * q);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) dst[k + 64u * q] = r[q];
-        }
     for (; k + 192u < hi; k += 256u) {
         const v4u32 a = __builtin_nontemporal_load(src + k), b = __builtin_nontemporal_load(src + k + 64u),
                     c = __builtin_nontemporal_load(src + k + 128u), d = __builtin_nontemporal_load(src + k + 192u);
@@ -119,36 +109,22 @@ out_copy_kernel_t(const v4u32 *__restrict__ src, v4u32 *__restrict__ dst, uint64
     for (; k < hi; k += 64u) dst[k] = __builtin_nontemporal_load(src + k);
 }
 
-static uint32_t out_copy_waves(uint32_t wg)                                     // XM_BAMDEV_COPY_WAVES (A/B): the waves themselves, not workgroups x 4
-{
-    static const long waves = [] { const char *v = getenv("XM_BAMDEV_COPY_WAVES"); return v && *v ? strtol(v, nullptr, 10) : 0L; }();
-    return waves > 0 ? (uint32_t)(waves > 16384 ? 16384 : waves) : 4u * wg;
-}
+// The copy's grid: eight one-wave workgroups.  The copy's stores wait in the same queues towards the fabric as the stores of the inflate launch beside it: the more
+// of them are in flight, the slower that launch, whether it reads its input over the link or from HBM (profiles/r06_ab_copy_wg.txt,
+// 4.5 GB of BAM -> 9.8 GB of text to /dev/null, one box, alternating): 4 waves 30.2-30.4 M pairs/s (the copy itself is the longest
+// party), 8: 38.5-39.4, 12: 37.6-37.8, 16: 36.8-37.2, 32: 34.4, 64: 31.8-31.9.  Eight waves, one per XCD, keep the link at ~50 GB/s
+// and the GPU's window (19.5 ms) and the copy's (18 ms) level, on a flat optimum (r06_ab_copy_deep.txt: 10 waves x 4 pieces and
+// 6 x 8 the same, 8 x 8 and 6 x 4 3 - 8 % slower).  The SAM path does not care (r06_ab_sam_copy_wg.txt).
+constexpr uint32_t OUT_COPY_GRID = 8;
 
-static void out_copy_launch(uint32_t grid, hipStream_t st, const v4u32 *src, v4u32 *dst, uint64_t n16)
+// `bytes` of the gathered stream at `src` (device) to `dst` (the host's page-locked, device-mapped buffer), on `st`
+static void out_copy(const uint8_t *src, uint8_t *dst, uint64_t bytes, hipStream_t st)
 {
-    static const bool deep = [] { const char *v = getenv("XM_BAMDEV_COPY_DEEP"); return v && v[0] == '8'; }();   // A/B: eight pieces per lane in flight
-    if (deep) out_copy_kernel_t<8><<<grid, 64, 0, st>>>(src, dst, n16);
-    else out_copy_kernel_t<4><<<grid, 64, 0, st>>>(src, dst, n16);
-}
-
-// Workgroups (x 4) of out_copy_kernel.  The copy's stores wait in the same queues towards the fabric as the stores of the inflate launch
-// beside it: the more of them are in flight, the slower that launch, whether it reads its input over the link or from HBM
-// (profiles/r06_ab_copy_wg.txt, 4.5 GB of BAM -> 9.8 GB of text to /dev/null, one box, alternating): 1 x 4 waves 30.2-30.4 M pairs/s
-// (the copy itself is the longest party), 2 x 4: 38.5-39.4, 3 x 4: 37.6-37.8, 4 x 4: 36.8-37.2, 8 x 4: 34.4, 16 x 4: 31.8-31.9 (the
-// default until the printer was ordered in front of the inflate launch: then it was the best of the sweep, r06_ab_bam_bins.txt).
-// Eight waves, one per XCD, keep the link at ~50 GB/s and the GPU's window (19.5 ms) and the copy's (18 ms) level.  The SAM path
-// shares the setting and does not care (r06_ab_sam_copy_wg.txt).  XM_BAMDEV_COPY_WG overrides (0: hipMemcpyAsync instead); A/B only:
-// XM_BAMDEV_COPY_WAVES (any number of waves) and XM_BAMDEV_COPY_DEEP=8 (eight pieces per lane in flight) -- 8 x 4 is on a flat
-// optimum (r06_ab_copy_deep.txt: 10 x 4 and 6 x 8 the same, 8 x 8 and 6 x 4 3 - 8 % slower).
-static uint32_t out_copy_workgroups()
-{
-    static const uint32_t wg = [] {
-        const char *v = getenv("XM_BAMDEV_COPY_WG");
-        const long n = v && *v ? strtol(v, nullptr, 10) : 2;
-        return (uint32_t)(n < 0 ? 0 : n > 4096 ? 4096 : n);
-    }();
-    return wg;
+    if (bytes == 0) return;
+    const uint64_t n16 = (bytes + 15u) / 16u;
+    const uint64_t waves = (n16 + 63u) / 64u;
+    out_copy_kernel<<<(uint32_t)(waves < OUT_COPY_GRID ? waves : OUT_COPY_GRID), 64, 0, st>>>(
+        reinterpret_cast<const v4u32 *>(src), reinterpret_cast<v4u32 *>(dst), n16);
 }
 
 // ---- the stream the output copy runs on ----
@@ -161,8 +137,8 @@ static uint32_t out_copy_workgroups()
 // 3 ms) for a word that a kernel on the candidate sets; on one queue the second cannot start before the first has ended, and the
 // word is never seen.  One copy stream serves both slots (two copies never need to overlap).  With 0 - 9 streams made by the
 // process beforehand the BAM path then runs at 39.0 - 40.6 M pairs/s throughout; a first candidate of the greatest priority (its
-// queues are apart from the ordinary ones on this runtime; XM_COPY_STREAM_PRIORITY=1) passes the test but copies 8 % slower in some
-// of those processes (34.8 - 38.9), and is not the default.  XM_COPY_STREAM_PROBE=0: the first candidate untested (A/B).
+// queues are apart from the ordinary ones on this runtime) passes the test but copies 8 % slower in some
+// of those processes (34.8 - 38.9), and is not used.
 __global__ void __launch_bounds__(64)
 probe_wait_kernel(volatile uint32_t *started_host, uint32_t *word, uint32_t *seen, unsigned long long max_ticks)
 {
@@ -211,21 +187,15 @@ static bool streams_run_side_by_side(hipStream_t a, hipStream_t b)
 // (also what makes a compute stream that has to run beside others: the SAM front end's second slot)
 static hipError_t create_copy_stream(hipStream_t *st, const hipStream_t *compute, int n_compute)
 {
-    static const bool probe = [] { const char *v = getenv("XM_COPY_STREAM_PROBE"); return !(v && v[0] == '0'); }();
-    static const bool prio = [] { const char *v = getenv("XM_COPY_STREAM_PRIORITY"); return v && v[0] == '1'; }();
     constexpr int TRIES = 8;
     hipStream_t tried[TRIES] = {};
     int n = 0, pick = -1;
     hipError_t e = hipSuccess;
     for (; n < TRIES && pick < 0; ++n) {
-        int least = 0, greatest = 0;
-        if (n == 0 && prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least)
-            e = hipStreamCreateWithPriority(&tried[n], hipStreamNonBlocking, greatest);
-        else
-            e = hipStreamCreateWithFlags(&tried[n], hipStreamNonBlocking);
+        e = hipStreamCreateWithFlags(&tried[n], hipStreamNonBlocking);
         if (e != hipSuccess) break;
         bool ok = true;
-        for (int c = 0; probe && ok && c < n_compute; ++c) ok = streams_run_side_by_side(compute[c], tried[n]);
+        for (int c = 0; ok && c < n_compute; ++c) ok = streams_run_side_by_side(compute[c], tried[n]);
         if (ok) pick = n;
     }
     if (pick < 0 && n > 0 && tried[0]) pick = 0;                                // none runs beside: the first one, as before

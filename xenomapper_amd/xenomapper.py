@@ -672,7 +672,6 @@ BAM_LINE_LIMIT = 1 << 32            # bam_lines gives up on a single SAM line lo
 FILE_WINDOW_BYTES = int(os.environ.get("XENOMAPPER_WINDOW_MB", "128")) << 20     # bytes of each file parsed per block
 FILE_MAX_RECORDS = 1 << 22
 STAGE_PIECE = 16 << 20              # bytes copied into page-locked memory per upload of the GPU stripper
-SAM_TAIL_ROOM = 16 << 20            # room in front of bytes read ahead for the tail of the window before them (at most a window)
 
 
 def _record_start(raw):
@@ -715,17 +714,7 @@ def _write_bytes(sink, data):
 
 
 MMAP_EMIT_MIN_BYTES = 1 << 20        # below this one buffered write is cheaper than mapping the file
-# bytes per background extension job (0: the whole extension in one).  Pieces let the writer go on as soon as the bytes it needs
-# are there, but every fallocate call beside the threads that fill the pages slows those: 32 MB pieces 5.9 - 7.0 M pairs/s, 8 MB
-# 5.5 - 6.0, one piece 7.7 - 7.9 (SAM text in, six files on tmpfs out, one box, profiles/r06_ab_ahead_piece.txt)
-AHEAD_PIECE = (int(os.environ.get("XENOMAPPER_AHEAD_PIECE_MB", "0")) << 20) or (1 << 62)
-MAP_AHEAD = int(os.environ.get("XENOMAPPER_MAP_AHEAD_MB", "1024")) << 20       # the writer's mapping of an output file reaches this far from where it was made (0: a mapping per call)
-AHEAD_MOST = int(os.environ.get("XENOMAPPER_AHEAD_MOST_MB", "1024")) << 20     # an output file is never extended further than this past its content
-# 1: extend the output files towards the size the run predicts from the fraction of the input it has read, instead of twice the last
-# call's bytes ahead.  Measured on one (slow) box, alternating (profiles/r06_ab_ahead_predict.txt): SAM text in 6.0 - 7.2 against
-# 5.3 - 6.1 M pairs/s, BAM in 10.5 - 12.4 against 13.6 - 15.9 -- the further the extension runs ahead, the more it takes from the
-# threads filling the pages behind it.  Not the default.
-AHEAD_PREDICT = os.environ.get("XENOMAPPER_AHEAD_PREDICT", "0") == "1"
+MAP_AHEAD = 1 << 30                  # the writer's mapping of an output file reaches this far from where it was made
 # (how far ahead: the further, the colder the pages when the writer's threads reach them -- x 2 fills at 0.22 - 0.31 s per 3.4 GB,
 # x 0.5 .. 1.5 at 0.14 - 0.18, with more waiting for the extension in exchange; x 1: profiles/r06_ab_ahead_factor.txt)
 AHEAD_FACTOR = float(os.environ.get("XENOMAPPER_AHEAD", "1"))      # output files are kept this many calls' worth of bytes longer than their content
@@ -791,9 +780,9 @@ class _AheadFile(object):
     instantiating pages (7 - 18 GB/s on tmpfs) and used to sit in front of every bin of every block; extended in the background,
     ahead of the writer, it is off the critical path.  The extension is a job in the helper pool towards a target the writer
     moves: XENOMAPPER_AHEAD (1) calls' worth of bytes past the content -- further ahead, the pages are cold again when the
-    writer's threads fill them.  (Measured and not the default: the extension in pieces, XENOMAPPER_AHEAD_PIECE_MB, each a job
-    of its own so that the writer waits for the piece it needs only; a target predicted from the fraction of the input read
-    so far, XENOMAPPER_AHEAD_PREDICT, at most AHEAD_MOST bytes ahead.)  finish() cuts the file back to its content.  Until
+    writer's threads fill them.  The whole extension is one fallocate: every call beside the threads that fill the pages slows
+    those, so pieces of it were slower (profiles/r06_ab_ahead_piece.txt), and so was a target predicted from the fraction of
+    the input read so far (profiles/r06_ab_ahead_predict.txt).  finish() cuts the file back to its content.  Until
     then the file ends in NUL bytes: a process killed between two blocks leaves them behind (the content in front of them is
     complete lines); only finish() -- reached on every exit of the run, exceptions included -- truncates."""
 
@@ -836,7 +825,7 @@ class _AheadFile(object):
 
     def _piece(self, pool):
         with self.cv:
-            start, n = self.size, min(AHEAD_PIECE, self.target - self.size)
+            start, n = self.size, self.target - self.size
         ok = n > 0
         if ok:
             try:
@@ -848,7 +837,7 @@ class _AheadFile(object):
                 self.size = max(self.size, start + n)
             else:
                 self.target = self.size
-            again = ok and self.size < self.target
+            again = ok and self.size < self.target          # extend_later() raised the target while this job ran
             if again:
                 try:
                     pool.submit(self._piece, pool)          # behind the other files' pieces and the unmapping jobs
@@ -898,16 +887,15 @@ class _AheadFile(object):
             os.close(self.fd2)
 
 
-def _emit_into_file(parser, paired, b, seg, sink, ahead=None, ahead_pool=None, ready=None, progress=None):
+def _emit_into_file(parser, paired, b, seg, sink, ahead=None, ahead_pool=None, ready=None):
     """The text of one bin's units written by the writer's threads STRAIGHT into the output file: the file is extended,
     its new pages are mapped, and xmh_emit gathers the lines into them in parallel -- no intermediate buffer and no
     single write(2) stream (which tops out at ~5 GB/s on one file and made the file path write-bound).  Only for a
     regular file positioned at its end, with an ASCII-compatible encoding and at least MMAP_EMIT_MIN_BYTES to write;
     False = not handled (the caller writes through the sink as before).  XENOMAPPER_MMAP_EMIT=0 switches it off.
-    ahead: {id(sink): _AheadFile} of the run -- with it the file stays extended past its content between calls (towards the size
-    it will have if the rest of the input -- progress: the fraction read so far -- fills it at the same rate; without a
-    fraction, twice the bytes of the last call), allocated by ahead_pool's threads while the next blocks are classified; the
-    run cuts the files back when it ends (_AheadFile.finish).
+    ahead: {id(sink): _AheadFile} of the run -- with it the file stays extended past its content between calls (by
+    XENOMAPPER_AHEAD times the bytes of the last call), allocated by ahead_pool's threads while the next blocks are classified;
+    the run cuts the files back when it ends (_AheadFile.finish).
     ready: the bin's text as it stands (uint8 array: the outputs of the window were gathered on the device, xm_bamdev_fetch_bins /
     xm_strip_fetch_bins) -- then the threads only copy it into the file's pages.  (Positional writes of the same ranges instead --
     one stream per file, or 8 MB chunks over 6 / 16 / 32 threads -- take 3.4 GB in 0.18 s when nothing else runs on the box
@@ -959,7 +947,7 @@ def _emit_into_file(parser, paired, b, seg, sink, ahead=None, ahead_pool=None, r
             size = pos + need
         t_m = time.perf_counter()
         own = None                                     # (address, length) of a mapping made for this call alone
-        if state is not None and MAP_AHEAD > 0 and ahead_pool is not None:
+        if state is not None and ahead_pool is not None:
             dst = state.window(pos, need, ahead_pool)  # the file's long mapping (made now, if the last one ends before pos + need)
         else:
             start = pos - pos % mmap.ALLOCATIONGRANULARITY
@@ -1015,14 +1003,7 @@ def _emit_into_file(parser, paired, b, seg, sink, ahead=None, ahead_pool=None, r
         if state is None:
             state = ahead[id(sink)] = _AheadFile(fd2, size)
         state.grew(size)
-        end = pos + need
-        if progress is not None and 0.0 < progress < 1.0:
-            upto = min(max(int(end / progress * 1.02), end + need // 2), end + AHEAD_MOST)
-        elif progress is not None:
-            upto = end                                 # the input has been read: nothing follows
-        else:
-            upto = end + int(AHEAD_FACTOR * need)
-        state.extend_later(ahead_pool, upto)
+        state.extend_later(ahead_pool, pos + need + int(AHEAD_FACTOR * need))
     elif state is None:
         os.close(fd2)
     return True
@@ -1080,19 +1061,6 @@ def _quietly(fn, *args):
         fn(*args)
     except Exception:                                                # noqa: BLE001
         pass
-
-
-def _input_fraction(sources):
-    """How far the run is through its input files (0 .. 1), or None when the sources do not say."""
-    done = total = 0
-    for src in sources:
-        if isinstance(src, _SamSource):
-            done, total = done + src.pos, total + int(src.raw.shape[0])
-        elif isinstance(src, _GpuBamFile):
-            done, total = done + src.cursor, total + int(src.data.shape[0])
-        else:
-            return None
-    return min(max(done / total, 0.0), 1.0) if total else None
 
 
 class _SamSource(object):
@@ -1490,11 +1458,6 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
         # Two parsers alternate so that the next window is decoded (BAM) and parsed in a helper thread -- the C++
         # code runs without the GIL -- while the GPU classifies and the writer emits the current one.
         parsers = [_host.Parser(n_threads), _host.Parser(n_threads)]
-        # pread(2) into the page-locked staging buffers by a SMALL pool of its own (XENOMAPPER_PREAD_THREADS): with the stripper
-        # on the GPU the helper thread only copies, and sixteen readers beside the writer's sixteen gatherers oversubscribe the
-        # cores that feed the PCIe link
-        n_readers = int(os.environ.get("XENOMAPPER_PREAD_THREADS", "0"))
-        reader_pool = _host.Parser(n_readers) if n_readers > 0 else None
         pool = ThreadPoolExecutor(max_workers=1)
         # output files extended ahead of the writer, their pages unmapped behind it (more helper threads than two measured no
         # better: profiles/r06_ab_sam_bins.txt)
@@ -1514,18 +1477,6 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
 
     # SAM text: the outputs gathered on the device as well (every bin needs a sink of its own; XENOMAPPER_GPU_SAM_BINS=0: the host gathers)
     sam_bins_on_device = stripper is not None and distinct and os.environ.get("XENOMAPPER_GPU_SAM_BINS", "1") != "0"
-    # ... and, with XENOMAPPER_SAM_READ_AHEAD=1, the bytes behind a window read (by a reader pool and a thread of their own) and
-    # sent over the link while it is stripped, instead of when it has said where it stopped.  Built to take the windows' serial
-    # dependency out of the run (a fifth of it, during which nothing is read), byte-exact, and measured: 13.6 - 18.7 against
-    # 13.1 - 14.3 M pairs/s to /dev/null on a box whose reads are slow, 14.4 - 17.7 against 17.2 - 20.0 on two where they are not
-    # (the reads, the link and the copy home then run all at once and each gets slower: profiles/r06_ab_sam_read_ahead.txt), no
-    # difference to files.  Not the default.
-    sam_spec, sam_slot_free, spec_reader, spec_pool = {}, {}, None, None
-    sam_prev_end, sam_last_tail = [None, None], [0, 0]
-    if (sam_bins_on_device and bamdev is None and os.environ.get("XENOMAPPER_SAM_READ_AHEAD", "0") == "1"
-            and os.environ.get("XM_STRIP_ZEROCOPY", "1") != "0"):
-        spec_reader = _host.Parser(int(os.environ.get("XENOMAPPER_SAM_READ_AHEAD_THREADS", "0")) or n_threads)
-        spec_pool = ThreadPoolExecutor(max_workers=1)
     bam_text = _BAM_TEXT_BUFFERS                                     # (slot, file) -> [text bytes, line_off, line_len] of the GPU BAM path
     bam_windows = [0]                                                # windows run so far
     # the records' SAM text is printed on the device when the reference names could be read (XENOMAPPER_GPU_BAM_TEXT=0: by the
@@ -1570,7 +1521,7 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
         full = want
         if bam_windows[0] < 2 and want >= (64 << 20):
             want = want >> (2 - bam_windows[0])
-            grow = 2.0 if os.environ.get("XENOMAPPER_BAM_AHEAD_GROW", "1") != "0" else 1.0
+            grow = 2.0
         bam_windows[0] += 1
         with prof("window"):
             if bam_ahead[0] is not None:                             # the read-ahead into this slot's staging buffers has ended
@@ -1722,31 +1673,9 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
         blk.finish = finish
         return blk, texts, [0, 0], eofs
 
-    def read_behind(slot, ends, counts, room):
-        """The bytes BEHIND the window that is being stripped -- [ends[f], ends[f] + counts[f]) of either file -- read into the other
-        slot's staging buffers, `room` bytes into them, and sent on to the device piece by piece as always: the next window begins
-        somewhere in the last bytes of this one (its walk will say where), so its tail is put in front of these bytes when it is
-        known (parse_next; include/xenomapper_strip.h, "reading ahead").  Runs beside the strip kernels, the fused pass and the
-        hand-over of the window in front, which used to be a fifth of a run during which nothing was read."""
-        t_r = time.perf_counter()
-        for f in (0, 1):
-            base = stripper.staging_address(slot, f)
-            stripper.begin_behind(slot, f, room)
-            for at in range(0, counts[f], STAGE_PIECE):
-                piece = min(STAGE_PIECE, counts[f] - at)
-                spec_reader.pread(sources[f].fileno(), ends[f] + at, base + room + at, piece)
-                stripper.upload(slot, f, room + at, piece)
-        prof["sam_read_behind"] = prof.get("sam_read_behind", 0.0) + time.perf_counter() - t_r
-
     def drop_stripper():
-        """The stripper is given up for the rest of the run (and of the process): not while a read into its buffers is under way."""
+        """The stripper is given up for the rest of the run (and of the process)."""
         nonlocal stripper
-        for sp in sam_spec.values():
-            try:
-                sp["job"].result()
-            except Exception:                                        # noqa: BLE001
-                pass
-        sam_spec.clear()
         _forget_stripper(stripper)
         stripper = None
 
@@ -1756,44 +1685,14 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
             return parse_next_bamdev(which, want)
         with prof("window"):
             wins = [src.window(want) for src in sources]
-        lead = [0, 0]                                                # bytes in front of each window's text in its staging buffer
-        ahead_of_us = sam_spec.pop(which, None)                      # bytes read behind the window in front, into this slot
-        if ahead_of_us is not None:
-            t_w = time.perf_counter()
-            try:
-                ahead_of_us["job"].result()
-            except Exception:                                        # noqa: BLE001 -- a read that failed: this window is read again
-                ahead_of_us = None
-            prof["sam_wait_read"] = prof.get("sam_wait_read", 0.0) + time.perf_counter() - t_w
-        for f in (0, 1):                                             # what the window in front left over of either file
-            if sam_prev_end[f] is not None:
-                sam_last_tail[f] = max(sam_prev_end[f] - wins[f][1], 0)
-        if ahead_of_us is not None and stripper is not None:
-            tails = [ahead_of_us["ends"][f] - wins[f][1] for f in (0, 1)]
-            if all(0 <= t <= ahead_of_us["room"] for t in tails):
-                # the window = its tail (read now: a few KB) + what was read ahead, right-aligned in the room in front of that
-                sizes = [int(src.raw.shape[0]) for src in sources]
-                for f in (0, 1):
-                    lead[f] = ahead_of_us["room"] - tails[f]
-                    n_f = tails[f] + ahead_of_us["counts"][f]
-                    wins[f] = (wins[f][0], wins[f][1], n_f, wins[f][1] + n_f >= sizes[f])
-                prof["sam_windows_read_ahead"] = prof.get("sam_windows_read_ahead", 0) + 1
-            else:
-                ahead_of_us = None                                   # the walk stopped further back than the room in front allows
         if stripper is not None and max(w[2] for w in wins) <= _ffi.STRIP_MAX_WINDOW:
             # no line of a record is shorter than two bytes with its terminator
             records = min(FILE_MAX_RECORDS, max(w[2] for w in wins) // 2 + 2)
             try:
-                need = max(lead[f] + wins[f][2] for f in (0, 1))
-                if spec_reader is not None and want <= _ffi.STRIP_MAX_WINDOW // 2:
-                    # (room for a window read ahead behind a gap, from the start: the buffers of a slot are never made again
-                    # while the main thread may still hold the window before -- see below)
-                    need = max(need, min(SAM_TAIL_ROOM, max(want, 1 << 16)) + want)
-                stripper.reserve(which, need, max(records, min(FILE_MAX_RECORDS, need // 2 + 2)))
+                stripper.reserve(which, max(w[2] for w in wins), records)
             except MemoryError:                                      # page-locked or device memory ran out: the host threads strip
                 drop_stripper()
         blk = None
-        sam_slot_free[which] = False                                 # until this window is known to go to the writer as six ranges
         if stripper is not None and max(w[2] for w in wins) <= _ffi.STRIP_MAX_WINDOW:
             try:
                 with prof("stage"):
@@ -1801,37 +1700,13 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                     # page of the inputs is mapped, and the writer gathers its lines from the staging buffer
                     for f, w in enumerate(wins):
                         base = stripper.staging_address(which, f)
-                        if ahead_of_us is not None:                  # all but the tail is there (and on the device) already
-                            if tails[f]:
-                                (reader_pool or parsers[which]).pread(sources[f].fileno(), w[1], base + lead[f], tails[f])
-                            stripper.set_lead(which, f, lead[f])
-                            continue
                         for at in range(0, w[2], STAGE_PIECE):
                             piece = min(STAGE_PIECE, w[2] - at)
-                            (reader_pool or parsers[which]).pread(sources[f].fileno(), w[1] + at, base + at, piece)
+                            parsers[which].pread(sources[f].fileno(), w[1] + at, base + at, piece)
                             stripper.upload(which, f, at, piece)
-                    # the bytes behind this window, into the other slot, while this one is stripped and handed over -- if the window
-                    # that slot held went to the writer as six ranges (then nobody reads its text any more) and both files go on
-                    other = which ^ 1
-                    if (spec_reader is not None and sam_slot_free.get(other, True) and not wins[0][3] and not wins[1][3]
-                            and want <= _ffi.STRIP_MAX_WINDOW // 2):
-                        room = min(SAM_TAIL_ROOM, max(want, 1 << 16))
-                        # (the main thread may still be counting the categories of the window that slot held, in the slot's
-                        # page-locked tables: only into buffers that are large enough as they stand)
-                        if stripper.fits(other, room + want, min(FILE_MAX_RECORDS, (room + want) // 2 + 2)):
-                            ends = [w[1] + w[2] for w in wins]
-                            # the two files hold the same reads at different bytes per record: the one whose windows leave the
-                            # longer tails gets that much less, or its tail would grow from window to window
-                            counts = [min(max(want - sam_last_tail[f], want // 2), int(sources[f].raw.shape[0]) - ends[f])
-                                      for f in (0, 1)]
-                            sam_spec[other] = {"ends": ends, "counts": counts, "room": room,
-                                               "job": spec_pool.submit(read_behind, other, ends, counts, room)}
-                sam_prev_end[0], sam_prev_end[1] = wins[0][1] + wins[0][2], wins[1][1] + wins[1][2]
                 with prof("strip"):
-                    blk = stripper.run(which, lead[0] + wins[0][2], wins[0][3], lead[1] + wins[1][2], wins[1][3], score_mode, paired,
+                    blk = stripper.run(which, wins[0][2], wins[0][3], wins[1][2], wins[1][3], score_mode, paired,
                                        skip_repeated, paired, records)
-                    if lead[0] or lead[1]:                           # (offsets count from the buffer's first byte: so much TEXT is done)
-                        blk.consumed = (blk.consumed[0] - lead[0], blk.consumed[1] - lead[1])
                     prof["strip_upload_ms"] = prof.get("strip_upload_ms", 0.0) + blk.ms_upload
                     prof["strip_kernels_ms"] = prof.get("strip_kernels_ms", 0.0) + blk.ms_kernels
             except (MemoryError, OSError):
@@ -1854,7 +1729,6 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                 if bins[0] == 0:
                     blk.bins = bins
                     prof["sam_windows_device_bins"] = prof.get("sam_windows_device_bins", 0) + 1
-                    sam_slot_free[which] = True                      # nobody reads this slot's staged text again
 
                     def finish(strip=stripper, slot=which):
                         t_w = time.perf_counter()
@@ -1867,9 +1741,8 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                 # more lines than the device tables hold, or a --cigar_scores block with a value the kernels do not vouch for:
                 # this window goes through the host stripper (the text is in the staging buffers already)
                 with prof("parse"):
-                    blk = parsers[which].parse(staged[0], lead[0], wins[0][2], wins[0][3], staged[1], lead[1], wins[1][2], wins[1][3],
+                    blk = parsers[which].parse(staged[0], 0, wins[0][2], wins[0][3], staged[1], 0, wins[1][2], wins[1][3],
                                                score_mode, paired, skip_repeated, paired, FILE_MAX_RECORDS)
-                return blk, staged, lead, [w[3] for w in wins]       # (the host stripper's offsets count from where it was told to begin)
             return blk, staged, [0, 0], [w[3] for w in wins]
         with prof("parse"):
             blk = None
@@ -1934,7 +1807,7 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                     if sinks[b] and boff[b + 1] > boff[b]:
                         piece = text[boff[b]:boff[b + 1]]
                         with prof("emit"):
-                            done = _emit_into_file(parser, paired, b, None, sinks[b], ahead, ahead_pool, ready=piece, progress=run_progress[0])
+                            done = _emit_into_file(parser, paired, b, None, sinks[b], ahead, ahead_pool, ready=piece)
                         if not done:
                             with prof("write"):
                                 _write_bytes(sinks[b], piece)
@@ -1944,7 +1817,7 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                     if limit is not None:
                         seg = seg[seg < limit]
                     with prof("emit"):
-                        done = _emit_into_file(parser, paired, b, seg, sinks[b], ahead, ahead_pool, progress=run_progress[0])
+                        done = _emit_into_file(parser, paired, b, seg, sinks[b], ahead, ahead_pool)
                         text = None if done else parser.emit(paired, b, seg, reuse=True)
                     with prof("write"):
                         _write_bytes(sinks[b], text)
@@ -1957,7 +1830,6 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
 
     which = 0
     future = None
-    run_progress = [None]                                            # fraction of the input behind the block being settled (None: not known)
     try:
         while True:
             try:
@@ -1981,8 +1853,6 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                 for f in (0, 1):
                     sources[f].advance(block.consumed[f], block.consumed_lines[f])
                 future = pool.submit(parse_next, which ^ 1, window)   # parse the next window while this one is classified
-            if AHEAD_PREDICT:
-                run_progress[0] = 1.0 if last else _input_fraction(sources)
             pending = settle(block, raws, pos, parsers[which], pending)
             if pending is not None:
                 raise pending
@@ -2006,18 +1876,10 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                         trouble = trouble or exc
             ahead_pool.shutdown(wait=True)
             pool.shutdown(wait=True)
-            if spec_pool is not None:
-                for sp in sam_spec.values():
-                    try:
-                        sp["job"].result()
-                    except Exception:                                # noqa: BLE001
-                        pass
-                spec_pool.shutdown(wait=True)
-                spec_reader.close()
             if bam_ahead_pool is not None:
                 bam_ahead_pool.shutdown(wait=True)
                 bam_reader.close()
-            for prs in parsers + ([reader_pool] if reader_pool is not None else []):
+            for prs in parsers:
                 prs.close()
             for src in sources:
                 if hasattr(src, "ahead_hits"):
