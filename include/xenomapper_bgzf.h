@@ -25,8 +25,8 @@
 extern "C" {
 #endif
 
-#define XMB_ABI_VERSION 3   /* 2: xm_bamdev_fetch_bins; f and B:f fields printed on the device.  3: raw1 / raw2 exist from the
-                               first xm_bamdev_fetch_raw on (xm_bamdev_raw) */
+#define XMB_ABI_VERSION 4   /* 2: xm_bamdev_fetch_bins; f and B:f fields printed on the device.  3: raw1 / raw2 exist from the
+                               first xm_bamdev_fetch_raw on (xm_bamdev_raw).  4: xm_bamdev_fetch_bins_bam */
 
 /* One BGZF block of the compressed image (24 bytes; the layout the kernels read). */
 typedef struct {
@@ -225,6 +225,20 @@ typedef struct {
     int32_t  status, reserved;
 } xm_bamdev_bins;
 int xm_bamdev_fetch_bins(xm_bamdev *b, int slot, uint64_t n_records, int paired, uint32_t sink_mask, xm_bamdev_bins *out);
+/* (e) after xm_bamdev_classify: the six outputs as BAM (XMB_ABI_VERSION 4) -- the alignment records of every bin whose sink is
+ * given, as they stand in the input and in the order of (d), inside BGZF members made of one stored DEFLATE block each (what
+ * `samtools view -u` writes; SAM specification 4.1, RFC 1951 3.2.4): records, frames and CRC-32s are made on the device, nothing
+ * is printed, and xm_bamdev_set_refs is not needed.  text = the page-locked stream, bin b's bytes = text[bin_off[b] .. bin_off[b + 1]):
+ * a whole number of complete members, none when the bin has no wanted unit.  The caller puts a BAM header in front of a sink's
+ * ranges and the 28-byte end-of-file member behind them.
+ * block_payload: record bytes per member, 64 .. 65280; 0 = 65280, htslib's value.  Every member but a bin's last holds exactly
+ * that many, so a record may span members (the specification allows it; xm_bamdev_run reports such a file as `unaligned`).
+ * ref_shift: added to refID and next_refID of file 2's records in bin 4 (`unresolved`, the one output that holds records of both
+ * files) where the field is >= 0, for a header whose reference list is file 1's followed by file 2's; 0 elsewhere.
+ * status 0: on its way (xm_bamdev_raw_wait); 2: more bytes than the slot's buffers hold (nothing was written: ask for (b)).
+ * There is no status 1: a binary64 field is bytes like any other here. */
+int xm_bamdev_fetch_bins_bam(xm_bamdev *b, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload,
+                             int32_t ref_shift, xm_bamdev_bins *out);
 /* the copies run on a stream of their own; this blocks until the one asked for last has arrived (any thread) */
 int xm_bamdev_raw_wait(xm_bamdev *b, int slot);
 /* the fused main loop on the slot's columns (as xm_strip_classify) */

@@ -73,10 +73,11 @@ def tiled_bam(src, dst, copies, aligned=True, level=6):
     return len(raw) - at
 
 
-def run(copies=4000, threads=0, workdir="/dev/shm", cigar_scores=False, single_end=False, to_files=False):
+def run(copies=4000, threads=0, workdir="/dev/shm", cigar_scores=False, single_end=False, to_files=False, bam_out=False):
     """One warm-up and one timed pass over the tiled fixtures; returns the result record (also bench.py's `e2e.bam`).
     cigar_scores: the --cigar_scores plugin (AS made of NM + CIGAR) instead of the AS / XS tags.  single_end: the files as
-    single-end input, as the command line runs it: the skipping walk (every run of equal names yields its first record)."""
+    single-end input, as the command line runs it: the skipping walk (every run of equal names yields its first record).
+    bam_out: output_format="bam" -- the records as they stand, gathered and BGZF-framed on the device, instead of their SAM text."""
     import types
     a = types.SimpleNamespace(copies=copies, threads=threads, dir=workdir)
     from xenomapper_amd import _host, xenomapper as xm
@@ -87,8 +88,9 @@ def run(copies=4000, threads=0, workdir="/dev/shm", cigar_scores=False, single_e
         paths.append(path)
     size = sum(os.path.getsize(p) for p in paths)
     names = ("primary_specific", "secondary_specific", "primary_multi", "secondary_multi", "unassigned", "unresolved")
-    out_paths = [os.path.join(a.dir, "xm_bam_out_%s_%d.sam" % (k, os.getpid())) for k in names] if to_files else []
+    out_paths = [os.path.join(a.dir, "xm_bam_out_%s_%d.%s" % (k, os.getpid(), "bam" if bam_out else "sam")) for k in names] if to_files else []
     sinks = {k: open(os.devnull, "wt") for k in names}
+    fmt = {"output_format": "bam"} if bam_out else {}
     try:
         xm.default_context()
         first = None
@@ -99,11 +101,11 @@ def run(copies=4000, threads=0, workdir="/dev/shm", cigar_scores=False, single_e
                 sinks = {k: open(p_, "wt") for k, p_ in zip(names, out_paths)}
             t0 = time.perf_counter()
             counts = xm.classify_sam_files(paths[0], paths[1], paired=not single_end, n_threads=a.threads, bam=True,
-                                           tag_func=xm.get_cigarbased_AS_tag if cigar_scores else xm.get_tag, **sinks)
+                                           tag_func=xm.get_cigarbased_AS_tag if cigar_scores else xm.get_tag, **fmt, **sinks)
             el = time.perf_counter() - t0
             first = el if first is None else first
         units = sum(counts.values())
-        return {"metric": "end-to-end %s/s (BAM in, six SAM files out)" % ("reads" if single_end else "read-pairs"), "value": units / el,
+        return {"metric": "end-to-end %s/s (BAM in, six %s files out)" % ("reads" if single_end else "read-pairs", "BAM" if bam_out else "SAM"), "value": units / el,
                 "plugin": "get_cigarbased_AS_tag" if cigar_scores else "get_tag", "units": units, "seconds": el, "first_run_seconds": first, "bam_bytes": size, "bam_GBps": size / el / 1e9,
                 "threads": a.threads or _host.lib().xmh_default_threads(),
                 "phases": {k: round(v, 4) for k, v in xm.LAST_FILE_PROFILE.items()}}
@@ -123,8 +125,9 @@ def main():
     ap.add_argument("--cigar_scores", action="store_true")
     ap.add_argument("--single_end", action="store_true")
     ap.add_argument("--files", action="store_true", help="six real output files in --dir instead of /dev/null")
+    ap.add_argument("--bam-out", action="store_true", help="BAM outputs (records framed on the device) instead of SAM text")
     a = ap.parse_args()
-    print(json.dumps(run(a.copies, a.threads, a.dir, a.cigar_scores, a.single_end, a.files)))
+    print(json.dumps(run(a.copies, a.threads, a.dir, a.cigar_scores, a.single_end, a.files, a.bam_out)))
 
 
 if __name__ == "__main__":

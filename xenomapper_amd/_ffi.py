@@ -171,6 +171,7 @@ def lib():
         "xm_bamdev_set_refs": ([P, I, P, P, ctypes.c_uint32], I),
         "xm_bamdev_fetch_text": ([P, I, U64, I, ctypes.c_uint32, P], I),
         "xm_bamdev_fetch_bins": ([P, I, U64, I, ctypes.c_uint32, P], I),
+        "xm_bamdev_fetch_bins_bam": ([P, I, U64, I, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, P], I),
         "xm_bamdev_classify": ([P, I, I, U64, I32, ctypes.POINTER(P), ctypes.POINTER(P), P, P], I),
         "xm_bamdev_columns": ([P, I, U64, P, P, P, P, P], I),
         "xm_bamdev_cigar_columns": ([P, I, I, U64, P, P, P, P, U64, ctypes.POINTER(ctypes.c_uint64)], I),
@@ -197,7 +198,7 @@ EXPORTED = ("xm_abi_version", "xm_strerror", "xm_last_hip_error", "xm_ctx_create
             "xms_abi_version", "xm_strip_create", "xm_strip_destroy", "xm_strip_reserve", "xm_strip_staging", "xm_strip_upload", "xm_strip_run",
             "xm_strip_classify", "xm_strip_fetch_bins", "xm_strip_out_wait", "xm_strip_columns", "xm_strip_cigar_columns", "xm_strip_device_columns", "xm_strip_last_error",
             "xm_bgzf_index", "xm_bgzf_index_prefix", "xm_bgzf_inflate_dev", "xm_bgzf_inflate_walk_dev", "xm_bgzf_crc32_dev", "xm_bgzf_strerror",
-            "xm_bamdev_create", "xm_bamdev_destroy", "xm_bamdev_reserve", "xm_bamdev_staging", "xm_bamdev_run", "xm_bamdev_raw_wait", "xm_bamdev_fetch_raw", "xm_bamdev_raw", "xm_bamdev_fetch_wanted", "xm_bamdev_fetch_text", "xm_bamdev_fetch_bins", "xm_bamdev_set_refs", "xm_bamdev_upload", "xm_bamdev_classify",
+            "xm_bamdev_create", "xm_bamdev_destroy", "xm_bamdev_reserve", "xm_bamdev_staging", "xm_bamdev_run", "xm_bamdev_raw_wait", "xm_bamdev_fetch_raw", "xm_bamdev_raw", "xm_bamdev_fetch_wanted", "xm_bamdev_fetch_text", "xm_bamdev_fetch_bins", "xm_bamdev_fetch_bins_bam", "xm_bamdev_set_refs", "xm_bamdev_upload", "xm_bamdev_classify",
             "xm_bamdev_columns", "xm_bamdev_cigar_columns", "xm_bamdev_last_error")
 
 
@@ -1186,6 +1187,21 @@ class BamDev(object):
         off = [int(v) for v in t.bin_off]
         text = _host_view(t.text, off[7], np.uint8) if off[7] else np.zeros(0, dtype=np.uint8)
         return 0, text, off
+
+    def fetch_bins_bam(self, slot, n_records, paired, sink_mask, block_payload=0, ref_shift=0):
+        """After classify(): the six outputs as BAM (xm_bamdev_fetch_bins_bam) -> (status, stream, bin_off): bin b's records, inside
+        complete BGZF members of stored blocks, = stream[bin_off[b]:bin_off[b + 1]] (a view of a page-locked buffer, valid after
+        raw_wait and until the next run on the slot).  block_payload: record bytes per member (0: 65280); ref_shift: added to the
+        reference ids of file 2's records in `unresolved`.  status 2: more bytes than the slot's buffers hold."""
+        t = _BamDevBins()
+        rc = self._L.xm_bamdev_fetch_bins_bam(self._h, int(slot), int(n_records), int(bool(paired)), int(sink_mask), int(block_payload),
+                                              int(ref_shift), ctypes.byref(t))
+        self._check(rc, "xm_bamdev_fetch_bins_bam")
+        if t.status != 0:
+            return int(t.status), None, None
+        off = [int(v) for v in t.bin_off]
+        stream = _host_view(t.text, off[7], np.uint8) if off[7] else np.zeros(0, dtype=np.uint8)
+        return 0, stream, off
 
     def upload(self, slot, file, nbytes):
         """The first nbytes of the slot's staging buffer go to the device now (xm_bamdev_upload); the next run is told `uploaded`."""

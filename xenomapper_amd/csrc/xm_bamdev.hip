@@ -583,6 +583,138 @@ line_fill_kernel(const uint8_t *__restrict__ raw1, const uint8_t *__restrict__ r
     }
 }
 
+// ---- O: the six outputs as BAM (xm_bamdev_fetch_bins_bam): the wanted records as they stand, in BGZF members of stored blocks ----
+// The same unit lists and the same scan as G, with the records' own sizes (want_kernel's 4 + block_size) in place of line lengths:
+// the scan is then the layout of the six PAYLOADS back to back, S_b = where bin b's begins, L_b = S_(b+1) - S_b.  A member carries
+// P payload bytes (the last of a bin what is left) inside 31 bytes of frame -- 18 of gzip header with the BC subfield, 5 of stored-
+// block header (01 LEN NLEN), 8 of CRC-32 and ISIZE -- so payload byte r of bin b lies at F_b + (r / P) * (P + 31) + 23 + r % P.
+// O1 derives F_b and the members' descriptors, O2 copies every record to where it belongs (a wave per record, split at the member
+// seams), the CRC kernel of the inflate path reads the payloads where they lie, O3 writes the frames around them.
+constexpr uint32_t BGZF_HEAD = 18, STORED_HEAD = 5, BGZF_TAIL = 8, BGZF_FRAME = BGZF_HEAD + STORED_HEAD + BGZF_TAIL;
+
+// what O1 leaves for O2: F_b (b = 0..6; [7] = the framed total) and the index of every bin's first member ([7] = how many there are)
+struct BamLayout { uint32_t frame_start[8], member_start[8]; };
+
+__device__ __forceinline__ void bam_layout_of(const uint32_t *__restrict__ starts, uint32_t P, BamLayout &l)
+{
+    uint32_t f = 0, m = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 7u; ++b) {
+        l.frame_start[b] = f; l.member_start[b] = m;
+        const uint32_t len = starts[b + 1u] - starts[b], members = (len + P - 1u) / P;
+        f += len + members * BGZF_FRAME;
+        m += members;
+    }
+    l.frame_start[7] = f; l.member_start[7] = m;
+}
+
+// O1: a lane per member: its descriptor for the CRC kernel (out_off: the payload's first byte in the framed stream, isize: its bytes)
+__global__ void __launch_bounds__(256)
+bam_layout_kernel(const uint32_t *__restrict__ starts, uint32_t P, uint32_t n_members, BamLayout *__restrict__ layout,
+                  xm_bgzf_block *__restrict__ members)
+{
+    BamLayout l;
+    bam_layout_of(starts, P, l);
+    const uint32_t m = blockIdx.x * 256u + threadIdx.x;
+    if (m == 0u) *layout = l;
+    if (m >= n_members || m >= l.member_start[7]) return;
+    uint32_t b = 0;
+#pragma unroll
+    for (uint32_t k = 1; k < 7u; ++k) b += (l.member_start[k] <= m) ? 1u : 0u;
+    const uint32_t k = m - l.member_start[b], len = starts[b + 1u] - starts[b], left = len - k * P;
+    xm_bgzf_block d;
+    d.cdata_off = 0; d.cdata_len = 0;
+    d.out_off = (uint64_t)l.frame_start[b] + (uint64_t)k * (P + BGZF_FRAME) + BGZF_HEAD + STORED_HEAD;
+    d.isize = left < P ? left : P;
+    members[m] = d;
+}
+
+// O2's copy of one record: `size` bytes at src become payload bytes [r, r + size) of the bin whose frames begin at `frames`.  A lane
+// takes 16 bytes of the record per step (an unaligned dwordx4 load; the last one of a record may reach up to 15 bytes behind it,
+// still inside the window's buffer, which ends 64 bytes behind its last record) and stores them with one dwordx4 where they lie in
+// one member, byte by byte at a seam and at the record's end.  shift != 0: refID and next_refID -- words 1 and 6 of the record,
+// counted from the block_size word: word 1 of the first piece, word 2 of the second -- move up by it where they name a reference.
+__device__ __forceinline__ void record_to_frames(const uint8_t *__restrict__ src, uint32_t size, uint8_t *__restrict__ frames, uint32_t r, uint32_t P,
+                                                 int32_t shift, uint32_t lane)
+{
+    for (uint32_t k = lane * 16u; k < size; k += 64u * 16u) {
+        v4u32_any v = *reinterpret_cast<const v4u32_any *>(src + k);
+        if (shift != 0) {
+            if (k == 0u && (int32_t)v[1] >= 0) v[1] += (uint32_t)shift;
+            if (k == 16u && (int32_t)v[2] >= 0) v[2] += (uint32_t)shift;
+        }
+        const uint32_t at = r + k, valid = size - k < 16u ? size - k : 16u;
+        uint32_t member = at / P, in = at - member * P;
+        uint8_t *dst = frames + (uint64_t)member * (P + BGZF_FRAME) + BGZF_HEAD + STORED_HEAD + in;
+        if (valid == 16u && in + 16u <= P) {
+            *reinterpret_cast<v4u32_any *>(dst) = v;
+        } else {
+#pragma unroll
+            for (uint32_t t = 0; t < 16u; ++t) {
+                if (t >= valid) break;
+                *dst++ = (uint8_t)(v[t >> 2] >> (8u * (t & 3u)));
+                if (++in == P) { in = 0; dst += BGZF_FRAME; }               // over the trailer, and the next member's two headers
+            }
+        }
+    }
+}
+
+// O2: a wave per (unit, record of the unit) in the order line_fill_kernel takes its lines: a paired unit is records i - 1 and i, and
+// `unresolved` takes file 1's record(s) and then file 2's.  usize / uplace: the units' payload bytes and places (G1, the size scan).
+__global__ void __launch_bounds__(256)
+record_fill_kernel(const uint8_t *__restrict__ raw1, const uint8_t *__restrict__ raw2, const uint32_t *__restrict__ rec_off1,
+                   const uint32_t *__restrict__ rec_off2, const uint32_t *__restrict__ idx, const unsigned long long *__restrict__ off,
+                   uint32_t n_units, uint32_t n_records, int paired, uint32_t sink_mask, const uint32_t *__restrict__ ws1,
+                   const uint32_t *__restrict__ ws2, const uint32_t *__restrict__ usize, const uint32_t *__restrict__ uplace,
+                   const uint32_t *__restrict__ starts, const BamLayout *__restrict__ layout, uint32_t P, int32_t ref_shift,
+                   uint8_t *__restrict__ out, uint32_t out_cap)
+{
+    const uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint32_t p = paired ? g >> 1 : g, j = paired ? g & 1u : 0u;
+    if (p >= n_units) return;
+    const uint32_t size = usize[p];
+    if (size == 0u) return;
+    const uint32_t bin = bin_of_place(p, off);
+    const uint32_t i = idx[p], files = files_of_bin(bin, sink_mask);
+    if (i >= n_records || (paired && i == 0u)) return;
+    const uint32_t rec = paired ? i - 1u + j : i;
+    const uint32_t frame0 = layout->frame_start[bin], frame1 = layout->frame_start[bin + 1u];
+    if (frame1 > out_cap || frame0 > frame1) return;                            // (the total was checked before the launch)
+    uint32_t r = uplace[p] - starts[bin];                                       // the unit's first payload byte inside its bin
+    if (r > starts[bin + 1u] - starts[bin] || size > starts[bin + 1u] - starts[bin] - r) return;
+    for (uint32_t f = 0; f < 2u; ++f) {
+        if (((files >> f) & 1u) == 0u) continue;
+        const uint32_t *ws = f ? ws2 : ws1;
+        const uint32_t first = paired ? ws[i - 1u] : 0u, mine = ws[rec];
+        if (mine != 0u)
+            record_to_frames((f ? raw2 : raw1) + (f ? rec_off2 : rec_off1)[rec], mine, out + frame0, r + (j ? first : 0u), P,
+                             (f == 1u && bin == 4u) ? ref_shift : 0, lane);
+        r += first + ws[i];                                                     // behind file 1's records of the unit: file 2's
+    }
+}
+
+// O3: a lane per member: the gzip header with the BC subfield (BSIZE = member size - 1), the stored block's header, CRC-32 and ISIZE
+__global__ void __launch_bounds__(256)
+bam_frame_kernel(const xm_bgzf_block *__restrict__ members, const uint32_t *__restrict__ crc, uint32_t n_members, uint8_t *__restrict__ out,
+                 uint32_t out_cap)
+{
+    const uint32_t m = blockIdx.x * 256u + threadIdx.x;
+    if (m >= n_members) return;
+    const xm_bgzf_block d = members[m];
+    const uint32_t len = d.isize, bsize = len + BGZF_FRAME - 1u;
+    if (d.out_off < BGZF_HEAD + STORED_HEAD || d.out_off + len + BGZF_TAIL > out_cap || len > 0xFFFFu - BGZF_FRAME + 1u) return;
+    uint8_t *h = out + d.out_off - (BGZF_HEAD + STORED_HEAD);
+    const uint8_t head[BGZF_HEAD + STORED_HEAD] = {
+        0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)bsize, (uint8_t)(bsize >> 8),
+        1, (uint8_t)len, (uint8_t)(len >> 8), (uint8_t)~len, (uint8_t)(~len >> 8)};
+#pragma unroll
+    for (uint32_t k = 0; k < BGZF_HEAD + STORED_HEAD; ++k) h[k] = head[k];
+    uint8_t *t = out + d.out_off + len;
+    const uint32_t c = crc[m];
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) { t[k] = (uint8_t)(c >> (8u * k)); t[4u + k] = (uint8_t)(len >> (8u * k)); }
+}
+
 // ---- --cigar_scores: the records' CIGAR words as the packed CIGAR columns K1p reads (include/xenomapper_hip.h) ------------------
 // BAM holds the operations as the kernel wants them (len << 4 | op); what is left to do is what xm_cigar_pack does on the host:
 // a count byte per record (255 = "255 or more": a trailer word n_ops << 4 | 15 behind the operations), the operations back to
@@ -784,6 +916,11 @@ struct Slot {
     uint8_t *d_packed_all = nullptr, *h_packed_all = nullptr;
     uint64_t packed_stride = 0;
     uint32_t *d_usize = nullptr, *d_uplace = nullptr, *d_upart = nullptr;      // per unit: bytes of its lines, where they go (fetch_bins)
+    // BAM outputs (xm_bamdev_fetch_bins_bam): the framed members' descriptors and CRCs, made when the first such call comes
+    xm_bgzf_block *d_members = nullptr;
+    uint32_t *d_member_crc = nullptr;
+    BamLayout *d_layout = nullptr;
+    uint64_t member_cap = 0;
     xm_bgzf_block *h_blocks = nullptr;
     xm_bgzf_walk *h_walk = nullptr;                         // per block: where its record chain starts and where its results go
     uint32_t *d_status = nullptr, *h_status = nullptr, *d_crc = nullptr, *h_crc = nullptr, *d_work = nullptr;
@@ -881,6 +1018,7 @@ void free_slot(Slot &sl)
     }
     dfree(sl.d_raw_all); dfree(sl.d_packed_all); hfree(sl.h_packed_all);
     dfree(sl.d_usize); dfree(sl.d_uplace); dfree(sl.d_upart);
+    dfree(sl.d_members); dfree(sl.d_member_crc); dfree(sl.d_layout); sl.member_cap = 0;
     hfree(sl.h_blocks); hfree(sl.h_walk); dfree(sl.d_status); hfree(sl.h_status); dfree(sl.d_crc); hfree(sl.h_crc);
     for (int c = 0; c < 4; ++c) dfree(sl.d_col[c]);
     dfree(sl.d_bits); dfree(sl.d_code); dfree(sl.d_bins4); dfree(sl.d_idx);
@@ -1632,6 +1770,82 @@ int xm_bamdev_fetch_bins(xm_bamdev *b, int slot, uint64_t n_records, int paired,
     sl.fill_issued = true;
     XMB_HIP(b, hipStreamWaitEvent(sl.copy_stream, sl.ev_inflated, 0));
     out_copy(sl.d_packed_all, sl.h_packed_all, total, sl.copy_stream);      // (the buffers end 64 bytes behind out_cap)
+    XMB_HIP(b, hipEventRecord(sl.ev_raw, sl.copy_stream));
+    sl.raw_issued = true;
+    if (hipGetLastError() != hipSuccess) return XM_ERR_HIP;
+    return XM_OK;
+}
+
+int xm_bamdev_fetch_bins_bam(xm_bamdev *b, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload,
+                             int32_t ref_shift, xm_bamdev_bins *out)
+{
+    if (!b || slot < 0 || slot > 1 || !out) return XM_ERR_INVALID_ARG;
+    Slot &sl = b->slot[slot];
+    if (n_records > sl.record_cap || n_records > 0xFFFFFFF0ull || !sl.have_columns || !sl.classified) return XM_ERR_INVALID_ARG;
+    const uint32_t P = block_payload ? block_payload : 65280u;
+    if (P < 64u || P > 65280u) return XM_ERR_INVALID_ARG;
+    memset(out, 0, sizeof *out);
+    out->text = sl.h_packed_all;
+    const uint32_t n = (uint32_t)n_records;
+    const uint64_t units64 = sl.h_off_counts[7];                                    // of the slot's last xm_bamdev_classify
+    if (n == 0 || units64 == 0) return XM_OK;
+    if (units64 > n_records) return XM_ERR_INVALID_ARG;
+    const uint32_t n_units = (uint32_t)units64;
+    XMB_HIP(b, hipSetDevice(b->device));
+    hipStream_t st = sl.stream;
+    const uint64_t out_cap = std::min<uint64_t>(2 * sl.packed_stride - 64u, 0xFFFFFFF0ull);
+    const uint32_t n_part = (n_units + SCAN_TILE - 1u) / SCAN_TILE;
+    const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(sl.d_off_counts);
+    XMB_HIP(b, hipMemsetAsync(sl.d_state + 13, 0, 13 * sizeof(uint32_t), st));
+    // W1 notes 4 + block_size of every record a sink takes: the bytes it has in a BAM file
+    want_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, sl.d_bins4, n, paired ? 1 : 0,
+                                                   sink_mask, sl.pf[0].d_wsize, sl.pf[1].d_wsize);
+    unit_size_kernel<<<(n_units + 255u) / 256u, 256, 0, st>>>(sl.d_idx, d_off, n_units, n, paired ? 1 : 0, sink_mask, sl.pf[0].d_wsize, sl.pf[1].d_wsize,
+                                                             sl.d_usize, reinterpret_cast<unsigned long long *>(sl.d_state + 24));
+    size_sum_kernel<<<n_part, 256, 0, st>>>(sl.d_usize, n_units, sl.d_upart);
+    part_scan_kernel<<<1, 1024, 0, st>>>(sl.d_upart, n_part, sl.d_state + 14);
+    size_place_kernel<true><<<n_part, 256, 0, st>>>(sl.d_usize, n_units, sl.d_upart, sl.d_uplace);
+    // where each bin's payload begins (state[16..23]; [14] the total)
+    bin_start_kernel<<<1, 64, 0, st>>>(sl.d_uplace, d_off, n_units, sl.d_state + 14, sl.d_state + 16);
+    XMB_HIP(b, hipMemcpyAsync(sl.h_state + 13, sl.d_state + 13, 13 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    XMB_HIP(b, hipEventRecord(sl.ev_wait, st));
+    XMB_HIP(b, hipEventSynchronize(sl.ev_wait));
+    if (hipGetLastError() != hipSuccess) return XM_ERR_HIP;
+    uint64_t total = 0;
+    memcpy(&total, sl.h_state + 24, sizeof total);                          // summed in 64 bits: the 32-bit places hold only if this fits
+    if (total > out_cap) { out->status = 2; return XM_OK; }
+    // the framed layout, as O1 derives it on the device: the same sums in 64 bits, against the same capacity, before anything is written
+    uint64_t framed = 0, n_members = 0;
+    for (int k = 0; k < 7; ++k) {
+        out->bin_off[k] = framed;
+        if (sl.h_state[17 + k] < sl.h_state[16 + k]) return XM_ERR_HIP;
+        const uint64_t len = sl.h_state[17 + k] - sl.h_state[16 + k], members = (len + P - 1u) / P;
+        framed += len + members * BGZF_FRAME;
+        n_members += members;
+    }
+    out->bin_off[7] = framed;
+    if (framed > out_cap) { memset(out->bin_off, 0, sizeof out->bin_off); out->status = 2; return XM_OK; }
+    if (n_members == 0) return XM_OK;
+    if (n_members > sl.member_cap) {                                        // (the slot's stream is idle: the wait above)
+        sl.member_cap = 0;
+        const size_t cap = (size_t)n_members + (size_t)n_members / 4 + 64;
+        XMB_TRY(dalloc(b, sl.d_members, cap)); XMB_TRY(dalloc(b, sl.d_member_crc, cap));
+        if (!sl.d_layout) XMB_TRY(dalloc(b, sl.d_layout, 1));
+        sl.member_cap = cap;
+    }
+    const uint32_t nm = (uint32_t)n_members;
+    bam_layout_kernel<<<(nm + 255u) / 256u, 256, 0, st>>>(sl.d_state + 16, P, nm, sl.d_layout, sl.d_members);
+    record_fill_kernel<<<((paired ? 2u : 1u) * n_units + 3u) / 4u, 256, 0, st>>>(
+        sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, sl.d_idx, d_off, n_units, n, paired ? 1 : 0, sink_mask,
+        sl.pf[0].d_wsize, sl.pf[1].d_wsize, sl.d_usize, sl.d_uplace, sl.d_state + 16, sl.d_layout, P, ref_shift, sl.d_packed_all, (uint32_t)out_cap);
+    const int rc = xm_bgzf_crc32_dev(b->ctx, st, sl.d_packed_all, sl.d_members, n_members, sl.d_member_crc);
+    if (rc != XM_OK) return rc;
+    bam_frame_kernel<<<(nm + 255u) / 256u, 256, 0, st>>>(sl.d_members, sl.d_member_crc, nm, sl.d_packed_all, (uint32_t)out_cap);
+    // the stream goes to the host on the copy stream behind the kernels (beside the next window's inflate launch on the other slot)
+    XMB_HIP(b, hipEventRecord(sl.ev_inflated, st));
+    sl.fill_issued = true;
+    XMB_HIP(b, hipStreamWaitEvent(sl.copy_stream, sl.ev_inflated, 0));
+    out_copy(sl.d_packed_all, sl.h_packed_all, framed, sl.copy_stream);     // (the buffers end 64 bytes behind out_cap)
     XMB_HIP(b, hipEventRecord(sl.ev_raw, sl.copy_stream));
     sl.raw_issued = true;
     if (hipGetLastError() != hipSuccess) return XM_ERR_HIP;

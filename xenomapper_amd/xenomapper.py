@@ -31,6 +31,7 @@ import math
 import os
 import re
 import stat
+import struct
 import sys
 import threading
 import time
@@ -140,12 +141,9 @@ def get_sam_header(samfile):
     return header
 
 
-def _bam_reader(bamfile, header_only=False):
-    """Native BGZF/BAM decoder over a binary file object (no samtools needed).  A regular file is memory-mapped
-    (nothing is read up front, nothing stays resident); anything else (a pipe, BytesIO) is read whole.
-    header_only: the handle that knows the header alone -- the file's blocks are not indexed (walking a multi-gigabyte
-    file's block headers through a mapping, and taking the mapping down again, was 0.3 s of the command line's 1.8 on 4.5 GB)."""
-    from . import _host
+def _bam_image(bamfile):
+    """The bytes of a binary file object as a uint8 array: a regular file is memory-mapped, anything else is read whole (and
+    rewound, as the reference's readers leave it)."""
     data = None
     try:
         fd = bamfile.fileno()
@@ -159,12 +157,27 @@ def _bam_reader(bamfile, header_only=False):
     if data is None:
         data = np.frombuffer(bamfile.read(), dtype=np.uint8)
         bamfile.seek(0)
+    return data
+
+
+def _bam_reader(bamfile, header_only=False):
+    """Native BGZF/BAM decoder over a binary file object (no samtools needed).  A regular file is memory-mapped
+    (nothing is read up front, nothing stays resident); anything else (a pipe, BytesIO) is read whole.
+    header_only: the handle that knows the header alone -- the file's blocks are not indexed (walking a multi-gigabyte
+    file's block headers through a mapping, and taking the mapping down again, was 0.3 s of the command line's 1.8 on 4.5 GB)."""
+    from . import _host
+    data = _bam_image(bamfile)
     return _host.BamReader(data, header_only=header_only)
 
 
 def get_bam_header(bamfile):
     """Header lines of a BAM file, as `samtools view -H` prints them (ref :48-54)."""
-    reader = _bam_reader(bamfile, header_only=True)
+    return _bam_header_lines(_bam_image(bamfile))
+
+
+def _bam_header_lines(data):
+    from . import _host
+    reader = _host.BamReader(data, header_only=True)
     try:
         return [line for line in reader.header().split("\n") if line]
     finally:
@@ -324,14 +337,41 @@ _HEADER_PLAN = (            # sink keyword, which input's header, @CO text   (re
 
 
 def process_headers(file1, file2, primary_specific=sys.stdout, secondary_specific=None, primary_multi=None,
-                    secondary_multi=None, unassigned=None, unresolved=None, bam=False):
+                    secondary_multi=None, unassigned=None, unresolved=None, bam=False, output_format="sam"):
     """Read both headers and write each open sink its header (ref :133-174).  primary_specific is
-    written unconditionally; secondary bins get file2's header, the rest file1's."""
-    reader = get_bam_header if bam else get_sam_header
-    headers = (reader(file1), reader(file2))
+    written unconditionally; secondary bins get file2's header, the rest file1's.
+    output_format="bam" (BAM inputs only): each sink gets a BGZF-framed BAM header instead -- the same text, and the reference
+    list of the input its records come from; `unresolved` holds records of both inputs and gets both lists
+    (_merge_unresolved_header).  Nothing is written when any sink has to be refused."""
+    if output_format not in ("sam", "bam"):
+        raise ValueError("output_format must be 'sam' or 'bam'")
+    if output_format == "bam" and not bam:
+        raise ValueError("BAM outputs need BAM inputs (bam=True)")
+    if output_format == "bam":
+        inputs = (_bam_image(file1), _bam_image(file2))
+        headers = tuple(_bam_header_lines(data) for data in inputs)
+    else:
+        reader = get_bam_header if bam else get_sam_header
+        headers = (reader(file1), reader(file2))
     sinks = dict(primary_specific=primary_specific, secondary_specific=secondary_specific,
                  primary_multi=primary_multi, secondary_multi=secondary_multi, unassigned=unassigned,
                  unresolved=unresolved)
+    if output_format == "bam":
+        keys = [key for key, _which, _comment in _HEADER_PLAN]
+        wrapped = dict(zip(keys, _bam_sinks([sinks[key] for key in keys])))
+        refs = tuple(_bam_header_of(data)[1] for data in inputs)
+        images = {}
+        for key, which, comment in _HEADER_PLAN:                     # every image is made before any is written
+            if wrapped[key]:
+                lines, ref_list = headers[which], refs[which]
+                if key == "unresolved":
+                    lines, ref_list = _merge_unresolved_header(headers[0], headers[1], refs[0], refs[1])
+                text = "\n".join(add_pg_tag(lines, comment=comment)) + "\n"
+                images[key] = _bgzf_frame(_bam_header_bytes(text, ref_list))
+        for key, _which, _comment in _HEADER_PLAN:
+            if key in images:
+                _write_bytes(wrapped[key], images[key])
+        return
     for key, which, comment in _HEADER_PLAN:
         if key == "primary_specific" or sinks[key]:
             print("\n".join(add_pg_tag(headers[which], comment=comment)), file=sinks[key])
@@ -1040,6 +1080,164 @@ def _resolve_exceptions(block, raws, pos, needed, tag_func, cigar_mode):
     return patches, None, None
 
 
+# --------------------------------------------------------------------------------------------
+# BAM outputs (output_format="bam"): the host's share -- header, framing, end-of-file marker, and the assembler of the windows
+# the device does not gather (SAM specification 4.1 BGZF, 4.2 BAM)
+# --------------------------------------------------------------------------------------------
+
+BGZF_PAYLOAD = 65280                # record bytes per member: htslib's value (a member never exceeds 64 KiB, however badly it deflates)
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")     # the empty member that ends a file (4.1.2)
+
+
+def _bgzf_frame(data, level=6, payload=BGZF_PAYLOAD):
+    """`data` as BGZF members of at most `payload` bytes each: gzip header with the BC subfield (BSIZE = member size - 1), a raw
+    DEFLATE stream, CRC-32 and ISIZE.  Nothing for no data."""
+    import zlib
+    view = memoryview(data).cast("B") if not isinstance(data, (bytes, bytearray)) else memoryview(data)
+    out = []
+    for at in range(0, len(view), payload):
+        piece = view[at:at + payload]
+        enc = zlib.compressobj(level, zlib.DEFLATED, -15)
+        body = enc.compress(piece) + enc.flush()
+        if len(body) + 26 > 65536:                                   # (cannot happen below 65280 bytes: deflate then stores)
+            raise ValueError("a BGZF member would exceed 64 KiB")
+        out.append(struct.pack("<4BI2BH2BHH", 0x1f, 0x8b, 8, 4, 0, 0, 0xff, 6, 0x42, 0x43, 2, len(body) + 25))
+        out.append(body)
+        out.append(struct.pack("<II", zlib.crc32(piece) & 0xFFFFFFFF, len(piece)))
+    return b"".join(out)
+
+
+def _parse_bam_header(head):
+    """(text, [(name, length)], bytes of the header) of the inflated bytes a BAM file begins with; None while `head` is too short."""
+    if len(head) < 12:
+        return None
+    if bytes(head[:4]) != b"BAM\x01":
+        raise ValueError("not a BAM file")
+    l_text = int.from_bytes(head[4:8], "little")
+    p = 8 + l_text
+    if len(head) < p + 4:
+        return None
+    n_ref = int.from_bytes(head[p:p + 4], "little")
+    p += 4
+    refs = []
+    for _ in range(n_ref):
+        if len(head) < p + 4:
+            return None
+        l_name = int.from_bytes(head[p:p + 4], "little")
+        if len(head) < p + 8 + l_name:
+            return None
+        name = bytes(head[p + 4:p + 4 + l_name]).split(b"\0", 1)[0]
+        refs.append((name, int.from_bytes(head[p + 4 + l_name:p + 8 + l_name], "little")))
+        p += 8 + l_name
+    return bytes(head[8:8 + l_text]), refs, p
+
+
+def _bam_header_of(data):
+    """(text, [(name, length)], bytes of the header) of a BAM image (uint8 array): its BGZF members (walked by xm_bgzf_index,
+    whatever gzip subfields stand beside BC) inflated until the header is complete.  The one reader of the reference list:
+    the BAM outputs' headers and _GpuBamFile use it."""
+    import zlib
+    head, at = bytearray(), 0
+    while at < data.shape[0]:
+        try:
+            blocks, _crc, nxt, _total = _ffi.bgzf_index(data, at, cap=16, prefix=True)
+        except ValueError:
+            break
+        for blk in blocks:
+            c0, cl = int(blk["cdata_off"]), int(blk["cdata_len"])
+            head += zlib.decompress(bytes(data[c0:c0 + cl]), -15)
+            got = _parse_bam_header(head)
+            if got is not None:
+                return got
+        if nxt <= at:
+            break
+        at = nxt
+    raise ValueError("the BAM header could not be read")
+
+
+def _bam_header_bytes(text, refs):
+    """The uncompressed BAM header: magic, l_text, text, n_ref, the reference list."""
+    text = text.encode("ascii") if isinstance(text, str) else bytes(text)
+    out = [b"BAM\x01", struct.pack("<i", len(text)), text, struct.pack("<i", len(refs))]
+    for name, length in refs:
+        out.append(struct.pack("<i", len(name) + 1) + bytes(name) + b"\0" + struct.pack("<i", length))
+    return b"".join(out)
+
+
+class _BamSink(object):
+    """A sink of BAM output as the writer sees its text sinks: bytes go to `buffer` as they stand.  Binary handles are their own
+    buffer; a text handle gives its `.buffer` (flushed first, so that nothing written as text is overtaken)."""
+    encoding = "ascii"
+
+    def __init__(self, sink):
+        raw = getattr(sink, "buffer", None)
+        if raw is None:
+            if isinstance(sink, io.TextIOBase) or not hasattr(sink, "write"):
+                raise TypeError("BAM output needs a binary sink or a text handle with a .buffer, not %r" % type(sink).__name__)
+            raw = sink
+        self.sink, self.buffer = sink, raw
+
+    def flush(self):
+        self.sink.flush()
+
+    def fileno(self):
+        return self.sink.fileno()
+
+
+def _bam_sinks(sinks):
+    """The given sinks wrapped for BAM output (None stays None); ValueError when two bins share one, TypeError for a sink that
+    cannot take bytes -- both before anything is written."""
+    given = [s for s in sinks if s]
+    if len(set(id(s) for s in given)) != len(given):
+        raise ValueError("BAM outputs need a sink of its own for every bin: two bins share one")
+    return [(_BamSink(s) if s else None) for s in sinks]
+
+
+def _merge_unresolved_header(header1, header2, refs1, refs2):
+    """The header of `unresolved`, the one output with records of both files: file 1's text with file 2's @SQ lines behind file 1's
+    last @SQ line, and file 1's reference list followed by file 2's (file 2's records get their reference ids shifted by
+    len(refs1)).  A name in both lists has no valid dictionary: ValueError naming the first."""
+    names1 = set(name for name, _len in refs1)
+    for name, _len in refs2:
+        if name in names1:
+            raise ValueError("reference %r is in both inputs: `unresolved` cannot be written as BAM (leave it out, or take SAM text)"
+                             % name.decode("ascii", "replace"))
+    sq2 = [line for line in header2 if line[:3] == "@SQ"]
+    last = max([k for k, line in enumerate(header1) if line[:3] == "@SQ"], default=(0 if header1 and header1[0][:3] == "@HD" else -1))
+    return header1[:last + 1] + sq2 + header1[last + 1:], list(refs1) + list(refs2)
+
+
+def _bam_records_of(seg, paired, b, raws, offs, ref_shift=0):
+    """The host assembler of one bin's records: for the units `seg` (pair indices, input order) the bytes of the records the bin
+    takes -- primary bins file 1's, secondary bins file 2's, `unresolved` (4) file 1's then file 2's; a paired unit is records
+    i - 1 and i -- from raws[f] (uint8 array) where offs[f][k] says pair k's record of file f begins (its block_size word).
+    ref_shift moves the reference ids of file 2's records in `unresolved`.  -> uint8 array."""
+    seg = np.asarray(seg, dtype=np.int64)
+    if seg.shape[0] == 0:
+        return np.zeros(0, dtype=np.uint8)
+    cols = []
+    for f in ((0, 1) if b == 4 else ((1,) if b in (1, 3) else (0,))):
+        for k in ((seg - 1, seg) if paired else (seg,)):
+            start = np.asarray(offs[f])[k].astype(np.int64)
+            size = raws[f][start[:, None] + np.arange(4)].astype(np.int64)
+            cols.append((f, start, 4 + (size[:, 0] | size[:, 1] << 8 | size[:, 2] << 16 | size[:, 3] << 24)))
+    per_unit = sum(c[2] for c in cols)
+    base = np.cumsum(per_unit) - per_unit                            # where each unit's bytes begin
+    out = np.empty(int(per_unit.sum()), dtype=np.uint8)
+    for f, start, size in cols:
+        first = np.cumsum(size) - size
+        within = np.arange(int(size.sum()), dtype=np.int64) - np.repeat(first, size)
+        out[np.repeat(base, size) + within] = raws[f][np.repeat(start, size) + within]
+        if b == 4 and f == 1 and ref_shift:
+            for field in (4, 24):                                    # refID, next_refID (counted from the block_size word)
+                at = (base + field)[:, None] + np.arange(4)
+                ids = out[at].copy().view("<i4")[:, 0]
+                ids = np.where(ids >= 0, ids + ref_shift, ids).astype("<i4")
+                out[at] = ids.view(np.uint8).reshape(-1, 4)
+        base = base + size
+    return out
+
+
 LAST_FILE_PROFILE = {}      # wall seconds per phase of the last file-to-file run (window / parse overlap classify / emit / write)
 
 
@@ -1278,7 +1476,8 @@ class _GpuBamFile(object):
             self.skip = at - int(blocks["out_off"][j])
         else:                                                        # no record at all
             self.cursor, self.skip = nxt, 0
-        self.ref_names = self._reference_names(blocks, at)           # for the device printer (None: could not be read)
+        self.ref_lengths = None
+        self.ref_names = self._reference_names(at)                   # for the device printer (None: could not be read)
         self.fd = os.open(path, os.O_RDONLY)
         self.carry = (0, 0, 0)                                       # (slot, offset, bytes) of the previous window's tail
         self.bytes_per_record = 0.0                                  # of the windows so far (0: not known yet)
@@ -1289,30 +1488,15 @@ class _GpuBamFile(object):
         self.ahead_hits = self.ahead_misses = 0                      # windows whose blocks read_ahead had in place / that stage() had to index and read itself
         self.last_comp = 0                                           # compressed bytes of the last window staged
 
-    def _reference_names(self, blocks, at):
-        """The reference names of the BAM header (SAM specification 4.2: magic, l_text, text, n_ref, then l_name, name, l_ref per
-        reference), from the inflated bytes in front of the first record."""
-        import zlib
+    def _reference_names(self, at):
+        """The reference names of the BAM header (_bam_header_of), which must end where the first record begins; their lengths
+        go to self.ref_lengths."""
         try:
-            head = bytearray()
-            for blk in blocks:
-                if len(head) >= at:
-                    break
-                c0, cl = int(blk["cdata_off"]), int(blk["cdata_len"])
-                head += zlib.decompress(bytes(self.data[c0:c0 + cl]), -15)
-            if len(head) < at or head[:4] != b"BAM\x01":
+            _text, refs, size = _bam_header_of(self.data)
+            if size != at:
                 return None
-            l_text = int.from_bytes(head[4:8], "little")
-            p = 8 + l_text
-            n_ref = int.from_bytes(head[p:p + 4], "little")
-            p += 4
-            names = []
-            for _ in range(n_ref):
-                l_name = int.from_bytes(head[p:p + 4], "little")
-                name = bytes(head[p + 4:p + 4 + l_name])
-                names.append(name.split(b"\0", 1)[0])
-                p += 4 + l_name + 4
-            return names if p == at else None
+            self.ref_lengths = [length for _name, length in refs]    # (BAM outputs copy the list: names and lengths)
+            return [name for name, _length in refs]
         except Exception:                                            # noqa: BLE001 -- the host printer does not need them
             return None
 
@@ -1426,9 +1610,11 @@ class _GpuBamFile(object):
         self.reader.close()
 
 
-def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_threads=0, bam=False, starts=None):
+def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_threads=0, bam=False, starts=None, out_bam=False):
     """The three main loops on two SAM (or BAM) *files*: same results as _run(mode, getReadPairs(...)), with the
-    text work done by the C++ stripper / writer.  Falls back to the Python reader when the input is not ASCII."""
+    text work done by the C++ stripper / writer.  Falls back to the Python reader when the input is not ASCII.
+    out_bam: the sinks (_BamSink, one per bin) get the units' alignment records as BGZF members instead of their SAM text -- the
+    windows the device takes gathered and framed there (xm_bamdev_fetch_bins_bam), the others assembled by _bam_records_of."""
     from . import _host
     ctx = default_context()
     paired = mode != _ffi.MODE_SE
@@ -1449,6 +1635,9 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
             bamdev = default_bamdev()
         except MemoryError:
             bamdev = None
+    if out_bam and bamdev is None:
+        raise RuntimeError("BAM outputs need the GPU BAM front end (BAM inputs, a min_score that is a number, XENOMAPPER_GPU_BAM "
+                           "not 0, and memory for its buffers)")
     with prof("open"):
         if bamdev is not None:
             sources = [_GpuBamFile(path, n_threads) for path in (path1, path2)]
@@ -1482,7 +1671,12 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
     # the records' SAM text is printed on the device when the reference names could be read (XENOMAPPER_GPU_BAM_TEXT=0: by the
     # host threads, from the packed records; a window with floating-point fields is printed that way in any case)
     bam_text_on_device = [False]
-    if bamdev is not None and os.environ.get("XENOMAPPER_GPU_BAM_TEXT", "1") != "0" and all(src.ref_names is not None for src in sources):
+    ref_shift = 0                                                    # BAM outputs: file 2's reference ids in `unresolved` (its list follows file 1's)
+    if out_bam and sinks[4]:
+        if sources[0].ref_names is None:
+            raise ValueError("the reference list of %s could not be read: `unresolved` cannot be written as BAM" % path1)
+        ref_shift = len(sources[0].ref_names)
+    if bamdev is not None and not out_bam and os.environ.get("XENOMAPPER_GPU_BAM_TEXT", "1") != "0" and all(src.ref_names is not None for src in sources):
         for f, src in enumerate(sources):
             bamdev.set_refs(f, src.ref_names)
         bam_text_on_device[0] = True
@@ -1490,6 +1684,9 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
     # gathering the lines; needs every bin to have a sink of its own -- two bins sharing one are written unit by unit, _emit_shared).
     # XENOMAPPER_GPU_BAM_BINS=0: the device prints, the host gathers (round 5's form)
     bam_bins_on_device = [bam_text_on_device[0] and distinct and os.environ.get("XENOMAPPER_GPU_BAM_BINS", "1") != "0"]
+    # BAM outputs: records gathered and framed on the device (xm_bamdev_fetch_bins_bam; XENOMAPPER_GPU_BAM_BINS=0: the packed records
+    # come back and the host assembles)
+    bam_out_on_device = out_bam and os.environ.get("XENOMAPPER_GPU_BAM_BINS", "1") != "0"
     # the GPU BAM path reads the next window's compressed blocks while the GPU works on the current one (_GpuBamFile.read_ahead):
     # a reader of its own (8 threads: pread into page-locked memory peaks there, e2e.host_ceilings) and one thread that drives it
     bam_reader = _host.Parser(8) if bamdev is not None and os.environ.get("XENOMAPPER_BAM_READ_AHEAD", "1") != "0" else None
@@ -1597,13 +1794,18 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                     first = inputs[f]["skip"] if not inputs[f]["carry_len"] else 0
                     n_rec, stop = _host.bam_walk(blk.raw_addr[f], blk.raw_len[f], first, rec)
                     rec = rec[:n_rec]
-                    text, _loff, _llen, got = print_records(which, f, blk.raw_addr[f], rec.ctypes.data, n_rec)
+                    text, loff, _llen, got = print_records(which, f, blk.raw_addr[f], rec.ctypes.data, n_rec)
                     texts.append((text, got))
-                    tables.append((rec, stop))
+                    tables.append((rec, stop, loff[:n_rec]))
                     sources[f].ran(which, blk.raw_len[f], rec, stop)
                 whole = [eofs[f] and tables[f][1] == blk.raw_len[f] for f in (0, 1)]
                 hb = parsers[which].parse(texts[0][0], 0, texts[0][1], whole[0], texts[1][0], 0, texts[1][1], whole[1],
                                           score_mode, paired, skip_repeated, paired, FILE_MAX_RECORDS)
+                if out_bam:
+                    # pair k of the text rules' walk is the record whose printed line begins where the parser's line k does
+                    # (under the skipping walk not record k)
+                    hb.bam_src = ([_ffi._host_view(blk.raw_addr[f], max(blk.raw_len[f], 1), np.uint8) for f in (0, 1)],
+                                  [tables[f][0][np.searchsorted(tables[f][2], hb.line_off[f][:hb.n])] for f in (0, 1)])
             return hb, [texts[0][0], texts[1][0]], [0, 0], eofs
         for f in (0, 1):
             sources[f].ran(which, blk.raw_len[f], consumed=blk.consumed[f] - inputs[f]["skip"], records=max(blk.n - (1 if paired else 0), 0))
@@ -1617,22 +1819,33 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                 mask = sum(1 << b for b in range(6) if sinks[b])
                 blk.lines = None
                 blk.bins = None
-                if bam_bins_on_device[0]:
-                    # the six outputs themselves, gathered on the device: what comes back is what the sinks get
-                    bins = bamdev.fetch_bins(which, blk.n, paired, mask)
-                    if bins[0] == 0:
-                        blk.bins = bins
-                if blk.bins is not None:
-                    prof["bam_windows_device_bins"] = prof.get("bam_windows_device_bins", 0) + 1
-                elif bam_text_on_device[0]:
-                    lines = bamdev.fetch_text(which, blk.n, paired, mask)
-                    if lines[0] == 0:
-                        blk.lines = lines
-                    # (status 1: a binary64 field -- f and B:f are printed on the device since round 6 --, 2: more text than the
-                    # slot's buffers hold: the host prints THIS window; the next one is offered to the device again)
-                if blk.lines is None and blk.bins is None:
-                    blk.packed = bamdev.fetch_wanted(which, blk.n, paired, mask)
-                key = "bam_windows_device_text" if (blk.lines is not None or blk.bins is not None) else "bam_windows_host_text"
+                if out_bam:
+                    # the six outputs as BAM: the records as they stand, gathered and framed on the device -- nothing is printed
+                    if bam_out_on_device:
+                        bins = bamdev.fetch_bins_bam(which, blk.n, paired, mask, 0, ref_shift)
+                        if bins[0] == 0:
+                            blk.bins = bins
+                    # (status 2 -- more bytes than the slot's buffers hold -- or XENOMAPPER_GPU_BAM_BINS=0: the packed records
+                    # come back and the host assembles)
+                    if blk.bins is None:
+                        blk.packed = bamdev.fetch_wanted(which, blk.n, paired, mask)
+                    key = "bam_windows_device_bam_bins" if blk.bins is not None else "bam_windows_host_bam"
+                else:
+                    if bam_bins_on_device[0]:
+                        # the six outputs themselves, gathered on the device: what comes back is what the sinks get
+                        bins = bamdev.fetch_bins(which, blk.n, paired, mask)
+                        if bins[0] == 0:
+                            blk.bins = bins
+                            prof["bam_windows_device_bins"] = prof.get("bam_windows_device_bins", 0) + 1
+                    if blk.bins is None and bam_text_on_device[0]:
+                        lines = bamdev.fetch_text(which, blk.n, paired, mask)
+                        if lines[0] == 0:
+                            blk.lines = lines
+                        # (status 1: a binary64 field -- f and B:f are printed on the device since round 6 --, 2: more text than the
+                        # slot's buffers hold: the host prints THIS window; the next one is offered to the device again)
+                    if blk.lines is None and blk.bins is None:
+                        blk.packed = bamdev.fetch_wanted(which, blk.n, paired, mask)
+                    key = "bam_windows_device_text" if (blk.lines is not None or blk.bins is not None) else "bam_windows_host_text"
                 prof[key] = prof.get(key, 0) + 1
         else:
             prof["bam_windows_raw"] = prof.get("bam_windows_raw", 0) + 1
@@ -1647,6 +1860,13 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                 prof["bam_wait_raw"] = prof.get("bam_wait_raw", 0.0) + time.perf_counter() - t_w
                 if getattr(blk, "bins", None) is not None:          # gathered on the device: the outputs themselves are here
                     return
+                if out_bam and blk.packed is not None:              # BAM outputs: the wanted records, packed -- the host assembles
+                    raw_addr, places, nbytes = blk.packed
+                    blk.bam_src = ([_ffi._host_view(raw_addr[f], max(nbytes[f], 1), np.uint8) for f in (0, 1)], list(places))
+                    return
+                if out_bam:                                          # ... or the whole windows and the table of the yielded records
+                    blk.bam_src = ([_ffi._host_view(blk.raw_addr[f], max(blk.raw_len[f], 1), np.uint8) for f in (0, 1)],
+                                   [_ffi._host_view(blk.rec_off_addr[f], max(blk.n, 1), np.uint32) for f in (0, 1)])
                 if getattr(blk, "lines", None) is not None:         # printed on the device: the text and its line table are here
                     _st, text, loff, llen = blk.lines
                     texts[0], texts[1] = text[0], text[1]
@@ -1778,7 +1998,7 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
         if err is not None:
             n, pending = bad, err                                # units closing at index >= bad are not reached
         ready = getattr(block, "bins", None) if (not exc and err is None) else None
-        if on_device and block.n and ready is None:
+        if on_device and block.n and ready is None and block.tables is not None:
             parser.adopt_lines(raws[0], pos[0], raws[1], pos[1], block.n, block.tables)
         if n:
             with prof("classify"):          # one fused pass: category bytes, counts and the six bin lists
@@ -1811,7 +2031,17 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                         if not done:
                             with prof("write"):
                                 _write_bytes(sinks[b], piece)
-            for b in (range(6) if (distinct and (ready is None or limit is not None)) else ()):
+            for b in (range(6) if (out_bam and (ready is None or limit is not None)) else ()):
+                if sinks[b]:
+                    # BAM outputs of a window the device did not gather: the same records through the host assembler
+                    seg = idx[int(off[b]):int(off[b + 1])]
+                    if limit is not None:
+                        seg = seg[seg < limit]
+                    with prof("emit"):
+                        data = _bgzf_frame(_bam_records_of(seg, paired, b, block.bam_src[0], block.bam_src[1], ref_shift), 1)
+                    with prof("write"):
+                        _write_bytes(sinks[b], data)
+            for b in (range(6) if (distinct and not out_bam and (ready is None or limit is not None)) else ()):
                 if sinks[b]:
                     seg = idx[int(off[b]):int(off[b + 1])]
                     if limit is not None:
@@ -1982,20 +2212,36 @@ def _finish_in_python(mode, path1, path2, pos, sinks, min_score, tag_func, skip_
 def classify_sam_files(primary_sam, secondary_sam, primary_specific=sys.stdout, secondary_specific=None,
                        primary_multi=None, secondary_multi=None, unassigned=None, unresolved=None, paired=False,
                        conservative=False, min_score=float("-inf"), tag_func=get_tag, skip_repeated_reads=None,
-                       n_threads=0, bam=False):
+                       n_threads=0, bam=False, output_format="sam"):
     """File-level entry point: classify two SAM files (paths) whose headers the caller has already dealt with
     (process_headers).  Equivalent to main_*(getReadPairs(open(primary_sam), open(secondary_sam), ...)) after the
     header lines, but parses and writes through the C++ stripper.  tag_func must be one of the three built-in
     plugins.  skip_repeated_reads defaults to `not paired`, as the command line does (ref :691).  bam=True: the
-    inputs are BAM files, decoded natively to the text `samtools view` would print."""
+    inputs are BAM files, decoded natively to the text `samtools view` would print.
+    output_format="bam" (bam=True only; process_headers with the same argument writes the headers): each sink gets its units'
+    alignment records as they stand in the inputs, in BGZF members of stored blocks framed on the GPU (what `samtools view -u`
+    writes), and the end-of-file marker after a run that succeeded.  The sinks are binary handles, or text handles with a
+    `.buffer`, one per bin.  Refused before anything is written: SAM inputs and shared sinks (ValueError), a sink without bytes
+    (TypeError), no GPU BAM front end (RuntimeError)."""
+    if output_format not in ("sam", "bam"):
+        raise ValueError("output_format must be 'sam' or 'bam'")
     if tag_func not in (get_tag, get_tag_with_ZS_as_XS, get_cigarbased_AS_tag):
         raise ValueError("classify_sam_files needs a built-in tag_func; use main_* for custom plugins")
     if skip_repeated_reads is None:
         skip_repeated_reads = not paired
     mode = _ffi.MODE_SE if not paired else (_ffi.MODE_PE_CONSERVATIVE if conservative else _ffi.MODE_PE_LIBERAL)
-    return _run_files(mode, primary_sam, secondary_sam,
-                      _sinks(primary_specific, secondary_specific, primary_multi, secondary_multi, unassigned, unresolved),
-                      min_score, tag_func, skip_repeated_reads, n_threads, bam)
+    sinks = _sinks(primary_specific, secondary_specific, primary_multi, secondary_multi, unassigned, unresolved)
+    if output_format == "bam":
+        if not bam:
+            raise ValueError("BAM outputs need BAM inputs (bam=True)")
+        sinks = _bam_sinks(sinks)
+        counts = _run_files(mode, primary_sam, secondary_sam, sinks, min_score, tag_func, skip_repeated_reads, n_threads, bam,
+                            out_bam=True)
+        for sink in sinks:                                           # (not after an exception: a file without the marker is truncated)
+            if sink:
+                _write_bytes(sink, BGZF_EOF)
+        return counts
+    return _run_files(mode, primary_sam, secondary_sam, sinks, min_score, tag_func, skip_repeated_reads, n_threads, bam)
 
 
 def _sinks(primary_specific, secondary_specific, primary_multi, secondary_multi, unassigned, unresolved):
@@ -2105,6 +2351,8 @@ def command_line_interface(*args, **kw):
         else:
             parser.add_argument("--" + flag, type=argparse.FileType(kind),
                                 default=sys.stdout if flag == "primary_specific" else None, help=text)
+    # (not in --help: its text is the reference's, byte for byte; README documents the flag)
+    parser.add_argument("--bam_outputs", action="store_true", help=argparse.SUPPRESS)
     ns = parser.parse_args(*args, **kw)
     if ns.version:
         print(__version__)
@@ -2113,6 +2361,8 @@ def command_line_interface(*args, **kw):
         print("ERROR: You must provide --primary_sam and --secondary_sam\n or --primary_bam and --secondary_bam\n")
         parser.print_help()
         sys.exit(1)
+    if ns.bam_outputs and (not ns.primary_bam or not ns.secondary_bam):
+        parser.error("--bam_outputs needs --primary_bam and --secondary_bam")
     return ns
 
 
@@ -2128,6 +2378,17 @@ def main(argv=None):
                  primary_multi=args.primary_multi, secondary_multi=args.secondary_multi,
                  unassigned=args.unassigned, unresolved=args.unresolved)
     skip_repeated = not args.paired
+    if args.bam_outputs:
+        # BAM in, BAM out: the records as they stand, framed on the GPU, through the handles' binary buffers
+        process_headers(args.primary_bam, args.secondary_bam, bam=True, output_format="bam", **sinks)
+        category_counts = classify_sam_files(args.primary_bam.name, args.secondary_bam.name, paired=args.paired,
+                                             conservative=args.conservative, min_score=args.min_score, tag_func=tag_func,
+                                             skip_repeated_reads=skip_repeated, bam=True, output_format="bam", **sinks)
+        output_summary(category_counts=category_counts, outfile=sys.stderr)
+        for sink in sinks.values():
+            if sink:
+                sink.flush()
+        return
     # regular files reach the C++ stripper / writer through the readpairs objects (see _ReadPairs); anything else is
     # split line by line in Python
     if args.primary_sam:
