@@ -321,3 +321,22 @@ def test_bam_frames_at_every_record_size(ctx, paired):
         assert min(refs2) < 0 <= max(refs2)
     finally:
         win.close()
+
+
+def test_classify_of_no_records_counts_as_classified_and_the_gathers_return_nothing(ctx):
+    """xm_bamdev_classify with n_records == 0 returns empty results without running the fused pass and MARKS the slot classified
+    (xm_bamdev_run cleared the mark), so xm_bamdev_fetch_bins and xm_bamdev_fetch_bins_bam of no records are accepted and return
+    status 0 with an empty stream.  (xm_strip_classify leaves the slot unclassified in the same case, and its fetch is refused:
+    tests/test_strip_shapes_gpu.py.)  Without any classify since the run the same fetch is refused with XM_ERR_INVALID_ARG."""
+    win = Window(ctx, S.shape_records(False, "spread"), False)
+    try:
+        assert win.n > 0
+        with pytest.raises(ValueError, match="xm_bamdev_fetch_bins"):
+            win.dev.fetch_bins(0, 0, False, ALL)
+        code, idx, off, counts = win.dev.classify(0, win.ffi.MODE_SE, 0, ABSENT)
+        assert code.shape[0] == 0 and idx.shape[0] == 0 and not off.any() and not counts.any()
+        for fetch in (win.dev.fetch_bins, win.dev.fetch_bins_bam):
+            status, stream, boff = fetch(0, 0, False, ALL)
+            assert status == 0 and boff == [0] * 8 and stream.shape[0] == 0
+    finally:
+        win.close()

@@ -345,3 +345,27 @@ def test_a_window_of_more_units_than_one_part_per_thread_of_the_scan():
         assert status == 0 and boff == [0] * 8 and text.shape[0] == 0
     finally:
         s.close()
+
+
+def test_classify_of_no_records_leaves_the_slot_unclassified(rig):
+    """xm_strip_classify with n_records == 0 returns empty results without running the fused pass and WITHOUT marking the slot
+    classified (xm_strip_run cleared the mark), so xm_strip_fetch_bins on the slot is refused with XM_ERR_INVALID_ARG, whatever
+    n_records it is given.  (xm_bamdev_classify marks the slot in the same case: tests/test_bam_shapes_gpu.py.)  A classify of the
+    block's records afterwards makes the same fetch succeed, and a fetch of no records then returns an empty stream."""
+    _ctx, s, p = rig
+    b1, b2, _state = binned_records(5, (0, 4), 5)
+    for slot in (0, 1):
+        got, want = compare(s, p, b1, b2, True, True, 0, False, False, 1 << 16, slot=slot)
+        assert want is not None and got.n == 5
+        code, idx, off, counts = s.classify(slot, MODES["single"][0], 0, ABSENT)
+        assert code.shape[0] == 0 and idx.shape[0] == 0 and not off.any() and not counts.any()
+        for n in (0, 5):
+            with pytest.raises(ValueError, match="xm_strip_fetch_bins"):
+                s.fetch_bins(slot, n, False, S.ALL)
+        _code, idx, off, _counts = s.classify(slot, MODES["single"][0], 5, ABSENT)
+        assert int(off[7]) == 5
+        status, text, boff = s.fetch_bins(slot, 5, False, S.ALL)
+        assert status == 0 and boff[7] > 0
+        s.out_wait(slot)
+        status, text, boff = s.fetch_bins(slot, 0, False, S.ALL)
+        assert status == 0 and boff == [0] * 8 and text.shape[0] == 0

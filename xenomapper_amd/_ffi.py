@@ -821,29 +821,10 @@ def _host_view(ptr, n, dtype):
     return np.frombuffer(buf, dtype=dtype, count=n)
 
 
-class StrippedBlock(object):
-    """One pair of windows stripped on the GPU (xm_strip_block): the walk's outcome and the line tables as NumPy views of
-    the stripper's page-locked arrays (valid until the slot is run again); the score columns stay on the device."""
-
-    def __init__(self, stripper, slot, raw):
-        self.stripper, self.slot = stripper, slot
-        n = self.n = int(raw.n_records)
-        self.consumed = (int(raw.consumed1), int(raw.consumed2))
-        self.consumed_lines = (int(raw.consumed_lines1), int(raw.consumed_lines2))
-        self.ended, self.starved, self.mismatch_at = bool(raw.ended), bool(raw.starved), int(raw.mismatch_at)
-        self.non_ascii = bool(raw.non_ascii)
-        self.overflow = bool(raw.overflow)
-        self.n_exceptions = int(raw.n_exceptions)
-        self.n_lines = (int(raw.n_lines1), int(raw.n_lines2))
-        self.tables = (raw.line_off1, raw.line_len1, raw.norm_len1, raw.line_flags1,
-                       raw.line_off2, raw.line_len2, raw.norm_len2, raw.line_flags2)
-        self.line_off = [_host_view(raw.line_off1, n, np.uint32), _host_view(raw.line_off2, n, np.uint32)]
-        self.line_len = [_host_view(raw.line_len1, n, np.uint32), _host_view(raw.line_len2, n, np.uint32)]
-        self.norm_len = [_host_view(raw.norm_len1, n, np.uint32), _host_view(raw.norm_len2, n, np.uint32)]
-        self.line_flags = [_host_view(raw.line_flags1, n, np.uint8), _host_view(raw.line_flags2, n, np.uint8)]
-        self.ms_upload, self.ms_kernels = float(raw.ms_upload), float(raw.ms_kernels)
-        self.csr = None
-        self._host_cols = None
+class _SlotBlock(object):
+    """What StrippedBlock and BamDevBlock share: the slot's columns on the host (asked of `stripper`, whoever classifies them)
+    and the flagged values of the line flags."""
+    _host_cols = None
 
     def _download(self):
         if self._host_cols is None:
@@ -876,23 +857,53 @@ class StrippedBlock(object):
         return out
 
 
-class Stripper(object):
-    """xm_strip: SAM text in page-locked staging buffers -> score columns in HBM + line tables on the host."""
+class StrippedBlock(_SlotBlock):
+    """One pair of windows stripped on the GPU (xm_strip_block): the walk's outcome and the line tables as NumPy views of
+    the stripper's page-locked arrays (valid until the slot is run again); the score columns stay on the device."""
+
+    def __init__(self, stripper, slot, raw):
+        self.stripper, self.slot = stripper, slot
+        n = self.n = int(raw.n_records)
+        self.consumed = (int(raw.consumed1), int(raw.consumed2))
+        self.consumed_lines = (int(raw.consumed_lines1), int(raw.consumed_lines2))
+        self.ended, self.starved, self.mismatch_at = bool(raw.ended), bool(raw.starved), int(raw.mismatch_at)
+        self.non_ascii = bool(raw.non_ascii)
+        self.overflow = bool(raw.overflow)
+        self.n_exceptions = int(raw.n_exceptions)
+        self.n_lines = (int(raw.n_lines1), int(raw.n_lines2))
+        self.tables = (raw.line_off1, raw.line_len1, raw.norm_len1, raw.line_flags1,
+                       raw.line_off2, raw.line_len2, raw.norm_len2, raw.line_flags2)
+        self.line_off = [_host_view(raw.line_off1, n, np.uint32), _host_view(raw.line_off2, n, np.uint32)]
+        self.line_len = [_host_view(raw.line_len1, n, np.uint32), _host_view(raw.line_len2, n, np.uint32)]
+        self.norm_len = [_host_view(raw.norm_len1, n, np.uint32), _host_view(raw.norm_len2, n, np.uint32)]
+        self.line_flags = [_host_view(raw.line_flags1, n, np.uint8), _host_view(raw.line_flags2, n, np.uint8)]
+        self.ms_upload, self.ms_kernels = float(raw.ms_upload), float(raw.ms_kernels)
+        self.csr = None
+
+
+class _FrontEnd(object):
+    """What Stripper and BamDev share: a handle of one family of the C API (_PREFIX: "xm_strip_" / "xm_bamdev_"), made on a
+    context and closed with it, and the calls both families have in one form."""
+    _PREFIX = None
+    _NO_CAP = None                                   # a slot's capacities before its first reserve
 
     def __init__(self, ctx):
         self._L = lib()
         self.ctx = ctx
         h = ctypes.c_void_p()
-        rc = self._L.xm_strip_create(ctx._h, ctx.device, ctypes.byref(h))
+        rc = self._fn("create")(ctx._h, ctx.device, ctypes.byref(h))
         if rc != XM_OK:
-            raise _ERRORS.get(rc, RuntimeError)("xm_strip_create: " + self._L.xm_strerror(rc).decode())
+            raise _ERRORS.get(rc, RuntimeError)(self._PREFIX + "create: " + self._L.xm_strerror(rc).decode())
         self._h = h
-        self._cap = [(0, 0)] * STRIP_SLOTS
+        self._cap = [self._NO_CAP] * STRIP_SLOTS
         ctx._strippers.add(self)
+
+    def _fn(self, name):
+        return getattr(self._L, self._PREFIX + name)
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.xm_strip_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -903,9 +914,60 @@ class Stripper(object):
 
     def _check(self, rc, what):
         if rc != XM_OK:
-            detail = self._L.xm_strip_last_error(self._h).decode()
+            detail = self._fn("last_error")(self._h).decode()
             raise _ERRORS.get(rc, RuntimeError)("%s: %s%s" % (what, self._L.xm_strerror(rc).decode(),
                                                                " [" + detail + "]" if detail and rc in (-3, -4) else ""))
+
+    @_one_call_per_context
+    def classify(self, slot, mode, n_records, min_score_floor):
+        """The fused pass on the slot's device columns -> (code, idx, bin_offsets, counts); code / idx are views of
+        page-locked arrays, valid until the next classify on the slot."""
+        code, idx = ctypes.c_void_p(), ctypes.c_void_p()
+        off = np.zeros(8, dtype=np.uint64)
+        counts = np.zeros(64, dtype=np.uint64)
+        rc = self._fn("classify")(self._h, slot, int(mode), int(n_records), int(min_score_floor), ctypes.byref(code),
+                                  ctypes.byref(idx), _np_ptr(off), _np_ptr(counts))
+        self._check(rc, self._PREFIX + "classify")
+        return (_host_view(code.value, int(n_records), np.uint8), _host_view(idx.value, int(off[7]), np.uint32), off, counts)
+
+    def _fetch_bins(self, name, *args):
+        """One of the fetch_bins calls (they fill the same structure) -> (status, stream, bin_off)."""
+        t = _BamDevBins()
+        self._check(self._fn(name)(self._h, *(list(args) + [ctypes.byref(t)])), self._PREFIX + name)
+        return self._bins_result(t)
+
+    @staticmethod
+    def _bins_result(t):
+        if t.status != 0:
+            return int(t.status), None, None
+        off = [int(v) for v in t.bin_off]
+        return 0, (_host_view(t.text, off[7], np.uint8) if off[7] else np.zeros(0, dtype=np.uint8)), off
+
+    def cigar_columns(self, slot, file, n_records):
+        """After a CIGAR-mode run: (nm int32, cig_cnt uint8, cig_tile uint32, cig_ops uint32) of one file, on the host."""
+        n = int(n_records)
+        nm = np.empty(n, dtype=np.int32)
+        cnt = np.empty(n, dtype=np.uint8)
+        tile = np.zeros(cigar_tiles(n) + 1, dtype=np.uint32)
+        n_ops = ctypes.c_uint64()
+        call, what = self._fn("cigar_columns"), self._PREFIX + "cigar_columns"
+        self._check(call(self._h, slot, file, n, _np_ptr(nm), _np_ptr(cnt), _np_ptr(tile), None, 0, ctypes.byref(n_ops)), what)
+        ops = np.zeros(max(int(n_ops.value), 1), dtype=np.uint32)
+        self._check(call(self._h, slot, file, n, None, None, None, _np_ptr(ops), ops.shape[0], ctypes.byref(n_ops)), what)
+        return nm, cnt, tile, ops[:int(n_ops.value)]
+
+    def columns(self, slot, n_records):
+        """-> [as1, xs1, as2, xs2 (int32), unit_bits (uint64)] copied to the host."""
+        n = int(n_records)
+        out = [np.empty(n, dtype=np.int32) for _ in range(4)] + [np.zeros((n + 63) // 64, dtype=np.uint64)]
+        if n:
+            self._check(self._fn("columns")(self._h, slot, n, *[_np_ptr(a) for a in out]), self._PREFIX + "columns")
+        return out
+
+
+class Stripper(_FrontEnd):
+    """xm_strip: SAM text in page-locked staging buffers -> score columns in HBM + line tables on the host."""
+    _PREFIX, _NO_CAP = "xm_strip_", (0, 0)
 
     def reserve(self, slot, window_bytes, max_records):
         have = self._cap[slot]
@@ -934,56 +996,15 @@ class Stripper(object):
         self._check(rc, "xm_strip_run")
         return StrippedBlock(self, slot, raw)
 
-    @_one_call_per_context
-    def classify(self, slot, mode, n_records, min_score_floor):
-        """The fused pass on the slot's device columns -> (code, idx, bin_offsets, counts); code / idx are views of
-        page-locked arrays, valid until the next classify on the slot."""
-        code, idx = ctypes.c_void_p(), ctypes.c_void_p()
-        off = np.zeros(8, dtype=np.uint64)
-        counts = np.zeros(64, dtype=np.uint64)
-        rc = self._L.xm_strip_classify(self._h, slot, int(mode), int(n_records), int(min_score_floor), ctypes.byref(code),
-                                       ctypes.byref(idx), _np_ptr(off), _np_ptr(counts))
-        self._check(rc, "xm_strip_classify")
-        return (_host_view(code.value, int(n_records), np.uint8), _host_view(idx.value, int(off[7]), np.uint32), off, counts)
-
     def fetch_bins(self, slot, n_records, paired, sink_mask):
         """After classify(): the six outputs themselves, gathered on the device (xm_strip_fetch_bins) -> (status, text, bin_off):
         bin b's text = text[bin_off[b]:bin_off[b + 1]] (a view of a page-locked buffer, valid after out_wait() and until the
         next fetch on the slot); status 2 / 3: this window is the host writer's (more text than the buffers hold / a wanted line
         that needs its white space re-joined)."""
-        t = _BamDevBins()                                               # (xm_strip_bins has the same layout)
-        rc = self._L.xm_strip_fetch_bins(self._h, int(slot), int(n_records), int(bool(paired)), int(sink_mask), ctypes.byref(t))
-        self._check(rc, "xm_strip_fetch_bins")
-        if t.status != 0:
-            return int(t.status), None, None
-        off = [int(v) for v in t.bin_off]
-        text = _host_view(t.text, off[7], np.uint8) if off[7] else np.zeros(0, dtype=np.uint8)
-        return 0, text, off
+        return self._fetch_bins("fetch_bins", int(slot), int(n_records), int(bool(paired)), int(sink_mask))     # (xm_strip_bins: the same layout)
 
     def out_wait(self, slot):
         self._check(self._L.xm_strip_out_wait(self._h, int(slot)), "xm_strip_out_wait")
-
-    def cigar_columns(self, slot, file, n_records):
-        """After a CIGAR-mode run: (nm int32, cig_cnt uint8, cig_tile uint32, cig_ops uint32) of one file, on the host."""
-        n = int(n_records)
-        nm = np.empty(n, dtype=np.int32)
-        cnt = np.empty(n, dtype=np.uint8)
-        tile = np.zeros(cigar_tiles(n) + 1, dtype=np.uint32)
-        n_ops = ctypes.c_uint64()
-        self._check(self._L.xm_strip_cigar_columns(self._h, slot, file, n, _np_ptr(nm), _np_ptr(cnt), _np_ptr(tile), None, 0,
-                                                   ctypes.byref(n_ops)), "xm_strip_cigar_columns")
-        ops = np.zeros(max(int(n_ops.value), 1), dtype=np.uint32)
-        self._check(self._L.xm_strip_cigar_columns(self._h, slot, file, n, None, None, None, _np_ptr(ops), ops.shape[0],
-                                                   ctypes.byref(n_ops)), "xm_strip_cigar_columns")
-        return nm, cnt, tile, ops[:int(n_ops.value)]
-
-    def columns(self, slot, n_records):
-        """-> [as1, xs1, as2, xs2 (int32), unit_bits (uint64)] copied to the host."""
-        n = int(n_records)
-        out = [np.empty(n, dtype=np.int32) for _ in range(4)] + [np.zeros((n + 63) // 64, dtype=np.uint64)]
-        if n:
-            self._check(self._L.xm_strip_columns(self._h, slot, n, *[_np_ptr(a) for a in out]), "xm_strip_columns")
-        return out
 
 
 # ---- include/xenomapper_bgzf.h: BAM records -> columns on the GPU (xm_bamdev_*) -----------------------------------------
@@ -1014,7 +1035,7 @@ class _BamDevBlock(ctypes.Structure):
                 ("flags1", ctypes.c_void_p), ("flags2", ctypes.c_void_p), ("ms_inflate", ctypes.c_float), ("ms_kernels", ctypes.c_float)]
 
 
-class BamDevBlock(object):
+class BamDevBlock(_SlotBlock):
     """One pair of BAM windows inflated and stripped on the GPU (xm_bamdev_block).  The score columns stay on the device; the
     inflated bytes and the record tables are page-locked host memory of the slot (valid until the slot runs again).  The
     caller prints the records' SAM text (set_text) before handing the block to the writer; then it looks like a StrippedBlock."""
@@ -1035,7 +1056,6 @@ class BamDevBlock(object):
         self.ms_inflate, self.ms_kernels = float(raw.ms_inflate), float(raw.ms_kernels)
         self.non_ascii = self.overflow = False
         self.csr = None
-        self._host_cols = None
         self.line_off = self.line_len = self.norm_len = self.tables = None
         self.packed = None                                       # fetch_wanted()'s result when only the wanted records came back
         self.finish = None                                       # set by the file path: prints the records' text when called
@@ -1047,52 +1067,10 @@ class BamDevBlock(object):
         self.tables = (line_off[0].ctypes.data, line_len[0].ctypes.data, line_len[0].ctypes.data, self.line_flags[0].ctypes.data,
                        line_off[1].ctypes.data, line_len[1].ctypes.data, line_len[1].ctypes.data, self.line_flags[1].ctypes.data)
 
-    def _download(self):
-        if self._host_cols is None:
-            self._host_cols = self.stripper.columns(self.slot, self.n)
-        return self._host_cols
 
-    @property
-    def cols(self):
-        return self._download()[:4]
-
-    @property
-    def unit_bits(self):
-        return self._download()[4]
-
-    exc = StrippedBlock.exc
-
-
-class BamDev(object):
+class BamDev(_FrontEnd):
     """xm_bamdev: BGZF blocks of two BAM files -> score columns in HBM, inflated bytes + record tables on the host."""
-
-    def __init__(self, ctx):
-        self._L = lib()
-        self.ctx = ctx
-        h = ctypes.c_void_p()
-        rc = self._L.xm_bamdev_create(ctx._h, ctx.device, ctypes.byref(h))
-        if rc != XM_OK:
-            raise _ERRORS.get(rc, RuntimeError)("xm_bamdev_create: " + self._L.xm_strerror(rc).decode())
-        self._h = h
-        self._cap = [(0, 0, 0, 0)] * 2
-        ctx._strippers.add(self)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.xm_bamdev_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != XM_OK:
-            detail = self._L.xm_bamdev_last_error(self._h).decode()
-            raise _ERRORS.get(rc, RuntimeError)("%s: %s%s" % (what, self._L.xm_strerror(rc).decode(),
-                                                               " [" + detail + "]" if detail and rc in (-3, -4) else ""))
+    _PREFIX, _NO_CAP = "xm_bamdev_", (0, 0, 0, 0)
 
     def reserve(self, slot, comp_bytes, raw_bytes, max_blocks, max_records):
         have = self._cap[slot]
@@ -1179,29 +1157,15 @@ class BamDev(object):
         """After classify(): the six outputs themselves, gathered on the device (xm_bamdev_fetch_bins) -> (status, text, bin_off):
         bin b's text = text[bin_off[b]:bin_off[b + 1]] (a view of a page-locked buffer, valid after raw_wait and until the next
         run on the slot); status 1 / 2: this window is the host's (a binary64 field / more text than the buffers hold)."""
-        t = _BamDevBins()
-        rc = self._L.xm_bamdev_fetch_bins(self._h, int(slot), int(n_records), int(bool(paired)), int(sink_mask), ctypes.byref(t))
-        self._check(rc, "xm_bamdev_fetch_bins")
-        if t.status != 0:
-            return int(t.status), None, None
-        off = [int(v) for v in t.bin_off]
-        text = _host_view(t.text, off[7], np.uint8) if off[7] else np.zeros(0, dtype=np.uint8)
-        return 0, text, off
+        return self._fetch_bins("fetch_bins", int(slot), int(n_records), int(bool(paired)), int(sink_mask))
 
     def fetch_bins_bam(self, slot, n_records, paired, sink_mask, block_payload=0, ref_shift=0):
         """After classify(): the six outputs as BAM (xm_bamdev_fetch_bins_bam) -> (status, stream, bin_off): bin b's records, inside
         complete BGZF members of stored blocks, = stream[bin_off[b]:bin_off[b + 1]] (a view of a page-locked buffer, valid after
         raw_wait and until the next run on the slot).  block_payload: record bytes per member (0: 65280); ref_shift: added to the
         reference ids of file 2's records in `unresolved`.  status 2: more bytes than the slot's buffers hold."""
-        t = _BamDevBins()
-        rc = self._L.xm_bamdev_fetch_bins_bam(self._h, int(slot), int(n_records), int(bool(paired)), int(sink_mask), int(block_payload),
-                                              int(ref_shift), ctypes.byref(t))
-        self._check(rc, "xm_bamdev_fetch_bins_bam")
-        if t.status != 0:
-            return int(t.status), None, None
-        off = [int(v) for v in t.bin_off]
-        stream = _host_view(t.text, off[7], np.uint8) if off[7] else np.zeros(0, dtype=np.uint8)
-        return 0, stream, off
+        return self._fetch_bins("fetch_bins_bam", int(slot), int(n_records), int(bool(paired)), int(sink_mask), int(block_payload),
+                                int(ref_shift))
 
     def upload(self, slot, file, nbytes):
         """The first nbytes of the slot's staging buffer go to the device now (xm_bamdev_upload); the next run is told `uploaded`."""
@@ -1209,34 +1173,3 @@ class BamDev(object):
 
     def raw_wait(self, slot):
         self._check(self._L.xm_bamdev_raw_wait(self._h, int(slot)), "xm_bamdev_raw_wait")
-
-    @_one_call_per_context
-    def classify(self, slot, mode, n_records, min_score_floor):
-        code, idx = ctypes.c_void_p(), ctypes.c_void_p()
-        off = np.zeros(8, dtype=np.uint64)
-        counts = np.zeros(64, dtype=np.uint64)
-        rc = self._L.xm_bamdev_classify(self._h, slot, int(mode), int(n_records), int(min_score_floor), ctypes.byref(code),
-                                        ctypes.byref(idx), _np_ptr(off), _np_ptr(counts))
-        self._check(rc, "xm_bamdev_classify")
-        return (_host_view(code.value, int(n_records), np.uint8), _host_view(idx.value, int(off[7]), np.uint32), off, counts)
-
-    def columns(self, slot, n_records):
-        n = int(n_records)
-        out = [np.empty(n, dtype=np.int32) for _ in range(4)] + [np.zeros((n + 63) // 64, dtype=np.uint64)]
-        if n:
-            self._check(self._L.xm_bamdev_columns(self._h, slot, n, *[_np_ptr(a) for a in out]), "xm_bamdev_columns")
-        return out
-
-    def cigar_columns(self, slot, file, n_records):
-        """After a SCORE_CIGAR run: (nm int32, cig_cnt uint8, cig_tile uint32, cig_ops uint32) of one file, made on the device."""
-        n = int(n_records)
-        nm = np.empty(n, dtype=np.int32)
-        cnt = np.empty(n, dtype=np.uint8)
-        tile = np.zeros(cigar_tiles(n) + 1, dtype=np.uint32)
-        n_ops = ctypes.c_uint64()
-        self._check(self._L.xm_bamdev_cigar_columns(self._h, slot, file, n, _np_ptr(nm), _np_ptr(cnt), _np_ptr(tile), None, 0,
-                                                    ctypes.byref(n_ops)), "xm_bamdev_cigar_columns")
-        ops = np.zeros(max(int(n_ops.value), 1), dtype=np.uint32)
-        self._check(self._L.xm_bamdev_cigar_columns(self._h, slot, file, n, None, None, None, _np_ptr(ops), ops.shape[0],
-                                                    ctypes.byref(n_ops)), "xm_bamdev_cigar_columns")
-        return nm, cnt, tile, ops[:int(n_ops.value)]

@@ -29,16 +29,12 @@
 
 #include <algorithm>
 #include <chrono>
-#include <mutex>
 #include <new>
-#include <string>
-#include <vector>
 
 #include "../../include/xenomapper_bgzf.h"
 #include "xm_bamrec.h"
 #include "xm_fmtg.h"
-#include "xm_gather.h"
-#include "xm_pinned.h"
+#include "xm_slot.h"
 
 namespace {
 
@@ -891,6 +887,7 @@ struct PerFile {
     uint8_t *d_ref_names = nullptr;
     uint32_t *d_ref_at = nullptr, n_refs = 0, *h_llen = nullptr;
     bool refs_set = false;
+    RefTable refs() const { return RefTable{d_ref_names, d_ref_at, n_refs}; }
     uint64_t llen_records = 0;
     // the skipping walk: the fields of the run starts, next to each other (ensure_skip), and their record starts on the host
     uint32_t *d_r_rec_off = nullptr, *d_r_name_off = nullptr, *d_r_name_len = nullptr, *d_r_ncig = nullptr, *d_r_cig_at = nullptr, *h_pair_off = nullptr;
@@ -904,7 +901,22 @@ struct PerFile {
     uint64_t table_len = 0;                 // entries of h_rec_off that are valid (the records of the slot's last window)
 };
 
-struct Slot {
+// Slot::d_state / h_state.  The record kernels and text_size_kernel address their words by these numbers.
+enum {
+    BS_MISMATCH = 0,     // first pair whose names differ (atomicMin; 0xFFFFFFFF: none)
+    BS_EXCEPTIONS = 1,   // pairs with a flagged value
+    BS_WEIRD = 2,        // bit 0: a record the text rules might read differently, bit 1: a malformed record
+    BS_OPEN_RUN = 3,     // the skipping walk: first run that may go on in the next window (atomicMin; 0xFFFFFFFF: none)
+    BS_RUNS = 4,         // [2]: run starts per file
+    BS_RUN_WORDS = 8,    // what xm_bamdev_run sets in front of the record kernels and reads back behind them ([6], [7]: spare)
+    BS_PACKED = 8,       // [2]: bytes per file of the packed records (xm_bamdev_fetch_wanted) or of the text (xm_bamdev_fetch_text)
+    BS_CIG_OPS = 10,     // [2]: words per file of the packed CIGAR operations (pack_cigar)
+    BS_GATHER = 12,      // the gather's block (xm_slot.h, GS_*); its GS_FLAG is text_size_kernel's state[13]: a field the host prints
+    BS_WORDS = 32
+};
+static_assert(BS_GATHER + GS_FLAG == 13 && BS_GATHER % 2 == 0 && BS_GATHER + GS_WORDS <= BS_WORDS, "text_size_kernel, 64-bit atomics");
+
+struct Slot : ClassifyOut, GatherPlan {               // (xm_slot.h: the columns and the classify outputs; the gathers' per-unit arrays)
     uint64_t comp_cap = 0, raw_cap = 0, block_cap = 0, record_cap = 0;
     PerFile pf[2];
     // both files' blocks are inflated by ONE launch (a window of one file is only a third of the blocks the chip can hold):
@@ -915,7 +927,6 @@ struct Slot {
     // xm_bamdev_fetch_bins prints the six outputs into them as one stream
     uint8_t *d_packed_all = nullptr, *h_packed_all = nullptr;
     uint64_t packed_stride = 0;
-    uint32_t *d_usize = nullptr, *d_uplace = nullptr, *d_upart = nullptr;      // per unit: bytes of its lines, where they go (fetch_bins)
     // BAM outputs (xm_bamdev_fetch_bins_bam): the framed members' descriptors and CRCs, made when the first such call comes
     xm_bgzf_block *d_members = nullptr;
     uint32_t *d_member_crc = nullptr;
@@ -924,12 +935,7 @@ struct Slot {
     xm_bgzf_block *h_blocks = nullptr;
     xm_bgzf_walk *h_walk = nullptr;                         // per block: where its record chain starts and where its results go
     uint32_t *d_status = nullptr, *h_status = nullptr, *d_crc = nullptr, *h_crc = nullptr, *d_work = nullptr;
-    int32_t *d_col[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t *d_bits = nullptr;
-    uint32_t *d_state = nullptr, *h_state = nullptr;
-    uint8_t *d_code = nullptr, *d_bins4 = nullptr, *h_code = nullptr;
-    uint32_t *d_idx = nullptr, *h_idx = nullptr;
-    uint64_t *d_off_counts = nullptr, *h_off_counts = nullptr;
+    uint32_t *d_state = nullptr, *h_state = nullptr;                           // BS_WORDS words
     hipStream_t stream = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_wait = nullptr;            // blocking-sync event: the waiting thread sleeps instead of spinning on a core the
@@ -945,58 +951,18 @@ struct Slot {
     bool raw_issued = false;                 // ev_raw has been recorded at least once (stays true: waiting for a past event costs nothing)
     bool fill_issued = false;                // ev_inflated was recorded behind a G2 launch (xm_bamdev_fetch_bins) at least once
     bool have_columns = false;
-    bool classified = false;                 // the fused pass has run on the slot's columns (its compact category stream is in d_bins4)
+    // what every fetch asks of the slot: columns of a run, classified
+    bool can_fetch(uint64_t n) const { return n <= record_cap && n <= 0xFFFFFFF0ull && have_columns && classified; }
 };
 
 }  // namespace
 
-struct xm_bamdev {
-    xm_ctx *ctx = nullptr;
-    int device = 0;
+struct xm_bamdev : FrontEnd {
     Slot slot[2];
-    std::mutex error_lock;
-    std::string last_error;
 };
 
+
 namespace {
-
-int fail(xm_bamdev *b, hipError_t e, const char *what)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    if (b) {
-        std::lock_guard<std::mutex> hold(b->error_lock);
-        b->last_error = buf;
-    }
-    (void)hipGetLastError();        // reported here: a later launch check on this thread must not find it again
-    return e == hipErrorOutOfMemory ? XM_ERR_OOM : XM_ERR_HIP;
-}
-
-#define XMB_HIP(b, call)                                   \
-    do {                                                   \
-        hipError_t e_ = (call);                            \
-        if (e_ != hipSuccess) return fail((b), e_, #call); \
-    } while (0)
-#define XMB_TRY(expr)                  \
-    do {                               \
-        int rc_ = (expr);              \
-        if (rc_ != XM_OK) return rc_;  \
-    } while (0)
-
-template <typename T> void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
-template <typename T> void hfree(T *&p) { if (p) { (void)xmpin::host_free(p); p = nullptr; } }
-template <typename T> int dalloc(xm_bamdev *b, T *&p, size_t count)
-{
-    dfree(p);
-    XMB_HIP(b, hipMalloc((void **)&p, std::max<size_t>(count, 16) * sizeof(T)));
-    return XM_OK;
-}
-template <typename T> int halloc(xm_bamdev *b, T *&p, size_t count)
-{
-    hfree(p);
-    XMB_HIP(b, xmpin::host_malloc((void **)&p, std::max<size_t>(count, 16) * sizeof(T)));
-    return XM_OK;
-}
 
 void free_slot(Slot &sl)
 {
@@ -1017,12 +983,10 @@ void free_slot(Slot &sl)
         q.skip_records = q.skip_cig_records = q.llen_records = 0; q.n_refs = 0;
     }
     dfree(sl.d_raw_all); dfree(sl.d_packed_all); hfree(sl.h_packed_all);
-    dfree(sl.d_usize); dfree(sl.d_uplace); dfree(sl.d_upart);
+    sl.free_units();
     dfree(sl.d_members); dfree(sl.d_member_crc); dfree(sl.d_layout); sl.member_cap = 0;
     hfree(sl.h_blocks); hfree(sl.h_walk); dfree(sl.d_status); hfree(sl.h_status); dfree(sl.d_crc); hfree(sl.h_crc);
-    for (int c = 0; c < 4; ++c) dfree(sl.d_col[c]);
-    dfree(sl.d_bits); dfree(sl.d_code); dfree(sl.d_bins4); dfree(sl.d_idx);
-    hfree(sl.h_code); hfree(sl.h_idx);
+    sl.release();
     sl.comp_cap = sl.raw_cap = sl.block_cap = sl.record_cap = 0;
 }
 
@@ -1035,21 +999,21 @@ static int ensure_cigar(xm_bamdev *b, Slot &sl)
         PerFile &q = sl.pf[f];
         if (q.cig_slots < q.slots_len) {
             q.cig_slots = 0;
-            XMB_TRY(dalloc(b, q.d_s_ncig, (size_t)q.slots_len)); XMB_TRY(dalloc(b, q.d_s_cig_at, (size_t)q.slots_len));
+            XMF_TRY(dalloc(b, q.d_s_ncig, (size_t)q.slots_len)); XMF_TRY(dalloc(b, q.d_s_cig_at, (size_t)q.slots_len));
             q.cig_slots = q.slots_len;
         }
         if (q.cig_records < sl.record_cap) {
             q.cig_records = 0;
             const size_t n = (size_t)sl.record_cap + 64;
-            XMB_TRY(dalloc(b, q.d_ncig, n)); XMB_TRY(dalloc(b, q.d_cig_at, n)); XMB_TRY(dalloc(b, q.d_cig_cnt, n));
-            XMB_TRY(dalloc(b, q.d_cig_tile, n / 256 + 8));
+            XMF_TRY(dalloc(b, q.d_ncig, n)); XMF_TRY(dalloc(b, q.d_cig_at, n)); XMF_TRY(dalloc(b, q.d_cig_cnt, n));
+            XMF_TRY(dalloc(b, q.d_cig_tile, n / 256 + 8));
             q.cig_records = sl.record_cap;
         }
         // the operations are words of the window; a record with 255 or more of them has one trailer word behind them
         const uint64_t need_ops = sl.raw_cap / 4u + sl.raw_cap / 1020u + 64u;
         if (q.ops_cap < need_ops) {
             q.ops_cap = 0;
-            XMB_TRY(dalloc(b, q.d_cig_ops, (size_t)need_ops));
+            XMF_TRY(dalloc(b, q.d_cig_ops, (size_t)need_ops));
             q.ops_cap = need_ops;
         }
     }
@@ -1064,14 +1028,14 @@ static int ensure_skip(xm_bamdev *b, Slot &sl, bool cigar)
         const size_t n = (size_t)sl.record_cap + 64;
         if (q.skip_records < sl.record_cap) {
             q.skip_records = 0;
-            XMB_TRY(dalloc(b, q.d_r_rec_off, n)); XMB_TRY(dalloc(b, q.d_r_name_off, n)); XMB_TRY(dalloc(b, q.d_r_name_len, n));
-            XMB_TRY(dalloc(b, q.d_r_a, n)); XMB_TRY(dalloc(b, q.d_r_x, n)); XMB_TRY(dalloc(b, q.d_r_flag, n));
-            XMB_TRY(halloc(b, q.h_pair_off, n));
+            XMF_TRY(dalloc(b, q.d_r_rec_off, n)); XMF_TRY(dalloc(b, q.d_r_name_off, n)); XMF_TRY(dalloc(b, q.d_r_name_len, n));
+            XMF_TRY(dalloc(b, q.d_r_a, n)); XMF_TRY(dalloc(b, q.d_r_x, n)); XMF_TRY(dalloc(b, q.d_r_flag, n));
+            XMF_TRY(halloc(b, q.h_pair_off, n));
             q.skip_records = sl.record_cap;
         }
         if (cigar && q.skip_cig_records < sl.record_cap) {
             q.skip_cig_records = 0;
-            XMB_TRY(dalloc(b, q.d_r_ncig, n)); XMB_TRY(dalloc(b, q.d_r_cig_at, n));
+            XMF_TRY(dalloc(b, q.d_r_ncig, n)); XMF_TRY(dalloc(b, q.d_r_cig_at, n));
             q.skip_cig_records = sl.record_cap;
         }
     }
@@ -1084,14 +1048,78 @@ static int pack_cigar(Slot &sl, int f, uint32_t n)
     PerFile &q = sl.pf[f];
     if (q.cig_records < n || q.ops_cap == 0 || n == 0) return XM_ERR_INVALID_ARG;
     hipStream_t st = sl.stream;
-    const uint32_t n_part = (n + SCAN_TILE - 1u) / SCAN_TILE;
     cig_size_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(q.v_ncig, n, q.d_cig_cnt, q.d_wsize);
-    size_sum_kernel<<<n_part, 256, 0, st>>>(q.d_wsize, n, q.d_part);
-    part_scan_kernel<<<1, 1024, 0, st>>>(q.d_part, n_part, sl.d_state + 10 + f);
-    size_place_kernel<true><<<n_part, 256, 0, st>>>(q.d_wsize, n, q.d_part, q.d_place);
-    cig_fill_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(q.d_raw, q.v_ncig, q.v_cig_at, q.d_place, sl.d_state + 10 + f, n, q.d_cig_tile, q.d_cig_ops,
+    scan_sizes<true>(st, q.d_wsize, n, q.d_part, q.d_place, sl.d_state + BS_CIG_OPS + f);
+    cig_fill_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(q.d_raw, q.v_ncig, q.v_cig_at, q.d_place, sl.d_state + BS_CIG_OPS + f, n, q.d_cig_tile, q.d_cig_ops,
                                                       (uint32_t)std::min<uint64_t>(q.ops_cap, 0xFFFFFFFFull));
     return XM_OK;
+}
+
+// W1: marks the records a sink takes and notes their sizes (d_wsize of both files)
+static void launch_want(Slot &sl, uint32_t n, int paired, uint32_t sink_mask)
+{
+    want_kernel<<<(n + 255u) / 256u, 256, 0, sl.stream>>>(sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, sl.d_bins4, n,
+                                                          paired ? 1 : 0, sink_mask, sl.pf[0].d_wsize, sl.pf[1].d_wsize);
+}
+
+// each file's packed records or text, the table of where each record's went and (lens) the line lengths, on the copy stream
+static int files_home(xm_bamdev *b, Slot &sl, const uint64_t bytes[2], uint32_t n, bool lens)
+{
+    for (int f = 0; f < 2; ++f) {
+        PerFile &q = sl.pf[f];
+        if (bytes[f]) XMF_HIP(b, hipMemcpyAsync(q.h_packed, q.d_packed, (size_t)bytes[f], hipMemcpyDeviceToHost, sl.copy_stream));
+        if (n) XMF_HIP(b, hipMemcpyAsync(q.h_place, q.d_place, (size_t)n * 4, hipMemcpyDeviceToHost, sl.copy_stream));
+        if (lens) XMF_HIP(b, hipMemcpyAsync(q.h_llen, q.d_wsize, (size_t)n * 4, hipMemcpyDeviceToHost, sl.copy_stream));
+    }
+    XMF_HIP(b, hipEventRecord(sl.ev_raw, sl.copy_stream));
+    sl.raw_issued = true;
+    return XM_OK;
+}
+
+// ---- the two gathers of the six outputs (text, BAM): what they share --------------------------------------------------
+struct BinsJob {
+    uint32_t n = 0, n_units = 0, *gs = nullptr;        // n_units == 0: nothing to gather; gs: the gather's state block on the device
+    uint64_t out_cap = 0;
+    const unsigned long long *d_off = nullptr;
+};
+
+// The opening: the checked numbers, the state block cleared, W1 queued.  XM_OK with n_units == 0: nothing to gather, or (status set)
+// the window is the host's.  text: line lengths and the places of the units are summed in 32 bits (as in xm_bamdev_fetch_text).
+static int begin_bins(xm_bamdev *b, Slot &sl, uint64_t n_records, int paired, uint32_t sink_mask, bool text, xm_bamdev_bins *out, BinsJob &job)
+{
+    memset(out, 0, sizeof *out);
+    out->text = sl.h_packed_all;
+    const uint64_t units64 = sl.h_off_counts[7];                                           // of the slot's last xm_bamdev_classify
+    if (n_records == 0 || units64 == 0) return XM_OK;
+    if (units64 > n_records) return XM_ERR_INVALID_ARG;
+    XMF_HIP(b, hipSetDevice(b->device));
+    if (text && (sl.pf[0].raw_len > 0x30000000ull || sl.pf[1].raw_len > 0x30000000ull)) { out->status = 2; return XM_OK; }
+    job.n = (uint32_t)n_records;
+    job.out_cap = std::min<uint64_t>(2 * sl.packed_stride - 64u, 0xFFFFFFF0ull);
+    job.d_off = reinterpret_cast<const unsigned long long *>(sl.d_off_counts);
+    job.gs = sl.d_state + BS_GATHER;
+    XMF_HIP(b, hipMemsetAsync(job.gs + GS_FLAG, 0, GS_LIVE_BYTES, sl.stream));
+    launch_want(sl, job.n, paired, sink_mask);
+    job.n_units = (uint32_t)units64;
+    return XM_OK;
+}
+
+// the units sized from the records' sizes in d_wsize, placed, the bins' starts known on the host
+static int place_bins(xm_bamdev *b, Slot &sl, const BinsJob &job, int paired, uint32_t sink_mask, Placed &at)
+{
+    unit_size_kernel<<<(job.n_units + 255u) / 256u, 256, 0, sl.stream>>>(sl.d_idx, job.d_off, job.n_units, job.n, paired ? 1 : 0, sink_mask,
+                                                                        sl.pf[0].d_wsize, sl.pf[1].d_wsize, sl.d_usize,
+                                                                        reinterpret_cast<unsigned long long *>(job.gs + GS_TOTAL64));
+    return sl.place_units(b, sl.stream, job.n_units, job.d_off, job.gs, sl.h_state + BS_GATHER, sl.ev_wait, at);
+}
+
+// the stream goes to the host on the copy stream behind the kernels (beside the next window's inflate launch on the other slot)
+static int bins_home(xm_bamdev *b, Slot &sl, uint64_t bytes)
+{
+    sl.fill_issued = true;
+    const int rc = Slot::send_home(b, sl.stream, sl.copy_stream, sl.ev_inflated, sl.ev_raw, sl.d_packed_all, sl.h_packed_all, bytes);
+    sl.raw_issued = true;                                                   // (the buffers end 64 bytes behind out_cap)
+    return rc;
 }
 
 extern "C" {
@@ -1111,10 +1139,9 @@ int xm_bamdev_create(xm_ctx *ctx, int device_id, xm_bamdev **out)
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.ev_wait, hipEventBlockingSync | hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.ev_inflated, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.ev_raw, hipEventBlockingSync | hipEventDisableTiming);
-        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_state, 32 * sizeof(uint32_t));
-        if (e == hipSuccess) e = xmpin::host_malloc((void **)&sl.h_state, 32 * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_off_counts, 72 * sizeof(uint64_t));
-        if (e == hipSuccess) e = xmpin::host_malloc((void **)&sl.h_off_counts, 72 * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_state, BS_WORDS * sizeof(uint32_t));
+        if (e == hipSuccess) e = xmpin::host_malloc((void **)&sl.h_state, BS_WORDS * sizeof(uint32_t));
+        if (e == hipSuccess) e = sl.create();
         if (e == hipSuccess) e = hipMalloc((void **)&sl.d_work, 16 * sizeof(uint32_t));
         for (int f = 0; f < 2 && e == hipSuccess; ++f) {
             PerFile &q = sl.pf[f];
@@ -1148,7 +1175,8 @@ int xm_bamdev_destroy(xm_bamdev *b)
         }
         if (sl.copy_stream) (void)hipStreamSynchronize(sl.copy_stream);
         free_slot(sl);
-        dfree(sl.d_state); hfree(sl.h_state); dfree(sl.d_off_counts); hfree(sl.h_off_counts);
+        sl.destroy();
+        dfree(sl.d_state); hfree(sl.h_state);
         dfree(sl.d_work);
         for (int f = 0; f < 2; ++f) { dfree(sl.pf[f].d_summary); hfree(sl.pf[f].h_summary); }
         for (int i = 0; i < 3; ++i)
@@ -1168,28 +1196,28 @@ int xm_bamdev_reserve(xm_bamdev *b, int slot, uint64_t comp_bytes, uint64_t raw_
     if (!b || slot < 0 || slot > 1 || raw_bytes >= 0xFFFF0000ull || comp_bytes >= 0xFFFF0000ull || max_blocks == 0 || max_records == 0 ||
         max_records >= 0xFFFFFF00ull || max_blocks >= 0x7FFFFF00ull)
         return XM_ERR_INVALID_ARG;
-    XMB_HIP(b, hipSetDevice(b->device));
+    XMF_HIP(b, hipSetDevice(b->device));
     Slot &sl = b->slot[slot];
-    XMB_HIP(b, hipStreamSynchronize(sl.stream));
-    if (sl.raw_issued) XMB_HIP(b, hipEventSynchronize(sl.ev_raw));            // THIS slot's last copy (the copy stream also carries the other slot's)
+    XMF_HIP(b, hipStreamSynchronize(sl.stream));
+    if (sl.raw_issued) XMF_HIP(b, hipEventSynchronize(sl.ev_raw));            // THIS slot's last copy (the copy stream also carries the other slot's)
     sl.have_columns = false;
     if (comp_bytes > sl.comp_cap) {
         sl.comp_cap = 0;
         sl.up_len[0] = sl.up_len[1] = 0;                                     // what was staged ahead went to the old buffer
         for (int f = 0; f < 2; ++f)
-            XMB_TRY(halloc(b, sl.pf[f].h_comp, (size_t)comp_bytes + XMB_COMP_PAD));      // (+ pad: the inflate launch reads it in place)
+            XMF_TRY(halloc(b, sl.pf[f].h_comp, (size_t)comp_bytes + XMB_COMP_PAD));      // (+ pad: the inflate launch reads it in place)
         sl.comp_cap = comp_bytes;
     }
     if (raw_bytes > sl.raw_cap) {
         sl.raw_cap = 0;
         sl.raw_stride = (raw_bytes + 64u + 255u) & ~(uint64_t)255;
-        XMB_TRY(dalloc(b, sl.d_raw_all, (size_t)(2 * sl.raw_stride)));
+        XMF_TRY(dalloc(b, sl.d_raw_all, (size_t)(2 * sl.raw_stride)));
         for (int f = 0; f < 2; ++f) {
             sl.pf[f].d_raw = sl.d_raw_all + f * sl.raw_stride;
             hfree(sl.pf[f].h_raw);                                           // made again, for the new capacity, by the next xm_bamdev_fetch_raw
         }
         sl.packed_stride = (raw_bytes + 64u + 255u) & ~(uint64_t)255;
-        XMB_TRY(dalloc(b, sl.d_packed_all, (size_t)(2 * sl.packed_stride))); XMB_TRY(halloc(b, sl.h_packed_all, (size_t)(2 * sl.packed_stride)));
+        XMF_TRY(dalloc(b, sl.d_packed_all, (size_t)(2 * sl.packed_stride))); XMF_TRY(halloc(b, sl.h_packed_all, (size_t)(2 * sl.packed_stride)));
         for (int f = 0; f < 2; ++f) {
             sl.pf[f].d_packed = sl.d_packed_all + f * sl.packed_stride;
             sl.pf[f].h_packed = sl.h_packed_all + f * sl.packed_stride;
@@ -1199,15 +1227,15 @@ int xm_bamdev_reserve(xm_bamdev *b, int slot, uint64_t comp_bytes, uint64_t raw_
     if (max_blocks > sl.block_cap) {
         sl.block_cap = 0;
         const size_t nb = (size_t)max_blocks + 2;
-        XMB_TRY(halloc(b, sl.h_blocks, 2 * nb));
-        XMB_TRY(halloc(b, sl.h_walk, 2 * nb));
-        XMB_TRY(dalloc(b, sl.d_status, 2 * nb)); XMB_TRY(halloc(b, sl.h_status, 2 * nb));
-        XMB_TRY(dalloc(b, sl.d_crc, 2 * nb)); XMB_TRY(halloc(b, sl.h_crc, 2 * nb));
+        XMF_TRY(halloc(b, sl.h_blocks, 2 * nb));
+        XMF_TRY(halloc(b, sl.h_walk, 2 * nb));
+        XMF_TRY(dalloc(b, sl.d_status, 2 * nb)); XMF_TRY(halloc(b, sl.h_status, 2 * nb));
+        XMF_TRY(dalloc(b, sl.d_crc, 2 * nb)); XMF_TRY(halloc(b, sl.h_crc, 2 * nb));
         for (int f = 0; f < 2; ++f) {
             PerFile &q = sl.pf[f];
             // segments: the blocks plus the pieces of a carried tail (at most as many again)
-            XMB_TRY(halloc(b, q.h_seg, 2 * nb + 4));
-            XMB_TRY(dalloc(b, q.d_cnt, 2 * nb + 4)); XMB_TRY(dalloc(b, q.d_exit, 2 * nb + 4)); XMB_TRY(dalloc(b, q.d_base, 2 * nb + 4));
+            XMF_TRY(halloc(b, q.h_seg, 2 * nb + 4));
+            XMF_TRY(dalloc(b, q.d_cnt, 2 * nb + 4)); XMF_TRY(dalloc(b, q.d_exit, 2 * nb + 4)); XMF_TRY(dalloc(b, q.d_base, 2 * nb + 4));
         }
         sl.block_cap = max_blocks;
     }
@@ -1216,21 +1244,15 @@ int xm_bamdev_reserve(xm_bamdev *b, int slot, uint64_t comp_bytes, uint64_t raw_
         const size_t n = (size_t)max_records + 64;
         for (int f = 0; f < 2; ++f) {
             PerFile &q = sl.pf[f];
-            XMB_TRY(dalloc(b, q.d_rec_off, n)); XMB_TRY(halloc(b, q.h_rec_off, n));
-            XMB_TRY(dalloc(b, q.d_name_off, n)); XMB_TRY(dalloc(b, q.d_name_len, n));
-            XMB_TRY(dalloc(b, q.d_a, n)); XMB_TRY(dalloc(b, q.d_x, n));
-            XMB_TRY(dalloc(b, q.d_rflag, n)); XMB_TRY(dalloc(b, q.d_lflag, n)); XMB_TRY(halloc(b, q.h_lflag, n));
-            XMB_TRY(dalloc(b, q.d_wsize, n)); XMB_TRY(dalloc(b, q.d_place, n)); XMB_TRY(halloc(b, q.h_place, n));
-            XMB_TRY(dalloc(b, q.d_part, n / SCAN_TILE + 8));
+            XMF_TRY(dalloc(b, q.d_rec_off, n)); XMF_TRY(halloc(b, q.h_rec_off, n));
+            XMF_TRY(dalloc(b, q.d_name_off, n)); XMF_TRY(dalloc(b, q.d_name_len, n));
+            XMF_TRY(dalloc(b, q.d_a, n)); XMF_TRY(dalloc(b, q.d_x, n));
+            XMF_TRY(dalloc(b, q.d_rflag, n)); XMF_TRY(dalloc(b, q.d_lflag, n)); XMF_TRY(halloc(b, q.h_lflag, n));
+            XMF_TRY(dalloc(b, q.d_wsize, n)); XMF_TRY(dalloc(b, q.d_place, n)); XMF_TRY(halloc(b, q.h_place, n));
+            XMF_TRY(dalloc(b, q.d_part, n / SCAN_TILE + 8));
         }
-        for (int c = 0; c < 4; ++c) XMB_TRY(dalloc(b, sl.d_col[c], n));
-        XMB_TRY(dalloc(b, sl.d_bits, n / 64 + 2));
-        XMB_TRY(dalloc(b, sl.d_code, n));
-        XMB_TRY(dalloc(b, sl.d_bins4, (size_t)XM_BINS4_BYTES(max_records) + 16));
-        XMB_TRY(dalloc(b, sl.d_idx, n));
-        XMB_TRY(dalloc(b, sl.d_usize, n)); XMB_TRY(dalloc(b, sl.d_uplace, n)); XMB_TRY(dalloc(b, sl.d_upart, n / SCAN_TILE + 8));
-        XMB_TRY(halloc(b, sl.h_code, n));
-        XMB_TRY(halloc(b, sl.h_idx, n));
+        XMF_TRY(sl.grow(b, max_records));
+        XMF_TRY(sl.reserve_units(b, max_records));
         sl.record_cap = max_records;
     }
     // the slots the inflate launch notes records in: slot_of() of the largest window and block count
@@ -1239,9 +1261,9 @@ int xm_bamdev_reserve(xm_bamdev *b, int slot, uint64_t comp_bytes, uint64_t raw_
         PerFile &q = sl.pf[f];
         if (need_slots > q.slots_len) {
             q.slots_len = 0;
-            XMB_TRY(dalloc(b, q.d_s_off, (size_t)need_slots)); XMB_TRY(dalloc(b, q.d_s_name_off, (size_t)need_slots));
-            XMB_TRY(dalloc(b, q.d_s_name_len, (size_t)need_slots)); XMB_TRY(dalloc(b, q.d_s_a, (size_t)need_slots));
-            XMB_TRY(dalloc(b, q.d_s_x, (size_t)need_slots)); XMB_TRY(dalloc(b, q.d_s_flag, (size_t)need_slots));
+            XMF_TRY(dalloc(b, q.d_s_off, (size_t)need_slots)); XMF_TRY(dalloc(b, q.d_s_name_off, (size_t)need_slots));
+            XMF_TRY(dalloc(b, q.d_s_name_len, (size_t)need_slots)); XMF_TRY(dalloc(b, q.d_s_a, (size_t)need_slots));
+            XMF_TRY(dalloc(b, q.d_s_x, (size_t)need_slots)); XMF_TRY(dalloc(b, q.d_s_flag, (size_t)need_slots));
             q.slots_len = need_slots;
         }
     }
@@ -1268,10 +1290,10 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
     out->mismatch_at = -1;
     sl.have_columns = false;
     sl.classified = false;
-    XMB_HIP(b, hipSetDevice(b->device));
-    if (cigar) XMB_TRY(ensure_cigar(b, sl));
+    XMF_HIP(b, hipSetDevice(b->device));
+    if (cigar) XMF_TRY(ensure_cigar(b, sl));
     const bool skip = skip_repeated != 0;
-    if (skip) XMB_TRY(ensure_skip(b, sl, cigar));
+    if (skip) XMF_TRY(ensure_skip(b, sl, cigar));
     hipStream_t st = sl.stream;
     static const bool profile = getenv("XM_BAMDEV_PROFILE") != nullptr;
     // The inflate launch reads the compressed blocks where the host staged them -- page-locked memory the device has mapped --
@@ -1288,15 +1310,15 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
     if (in[0].n_blocks + in[1].n_blocks > 2 * sl.block_cap) return XM_ERR_INVALID_ARG;
     // ---- stage: carry, compressed bytes, block tables; inflate + CRC; the record chain --------------------------------
     // this slot's previous window has left d_raw (its copy to the host ended long ago: the caller has printed from it)
-    if (sl.raw_issued) XMB_HIP(b, hipStreamWaitEvent(st, sl.ev_raw, 0));
+    if (sl.raw_issued) XMF_HIP(b, hipStreamWaitEvent(st, sl.ev_raw, 0));
     {
         // The OTHER slot's printer (G2 of the window in front) first: beside this window's inflate launch the two take 28 ms + 18 ms
         // where one after the other they take 6 + 17 (the decoder's window reads wait behind the printer's 6.6 GB of traffic: an
         // issue-bound launch turns latency-bound); profiles/r06_ab_serial_fill.txt.
         Slot &other = b->slot[slot ^ 1];
-        if (other.fill_issued) XMB_HIP(b, hipStreamWaitEvent(st, other.ev_inflated, 0));
+        if (other.fill_issued) XMF_HIP(b, hipStreamWaitEvent(st, other.ev_inflated, 0));
     }
-    XMB_HIP(b, hipEventRecord(sl.ev[0], st));
+    XMF_HIP(b, hipEventRecord(sl.ev[0], st));
     for (int f = 0; f < 2; ++f) {
         const xm_bamdev_input &x = in[f];
         PerFile &q = sl.pf[f];
@@ -1315,7 +1337,7 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
             if (x.carry_slot == slot && x.carry_off < x.carry_len) return XM_ERR_INVALID_ARG;          // would overlap itself
             // (the other slot's stream finished its window before the caller could know what to carry; its copy of the window
             // to the host may still be on its way)
-            XMB_HIP(b, hipMemcpyAsync(q.d_raw, src.d_raw + x.carry_off, (size_t)x.carry_len, hipMemcpyDeviceToDevice, st));
+            XMF_HIP(b, hipMemcpyAsync(q.d_raw, src.d_raw + x.carry_off, (size_t)x.carry_len, hipMemcpyDeviceToDevice, st));
         }
         q.raw_len = x.carry_len + new_bytes[f];
         // segments: the carry (when there is one), then every block; the launch's block table holds both files
@@ -1378,16 +1400,16 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
         int rc = xm_bgzf_inflate_walk_dev(b->ctx, st, sl.pf[0].h_comp, sl.h_blocks, n_all, sl.d_raw_all, sl.d_status, sl.d_work, sl.h_walk);
         if (rc == XM_OK) rc = xm_bgzf_crc32_dev(b->ctx, st, sl.d_raw_all, sl.h_blocks, n_all, sl.d_crc);
         if (rc != XM_OK) return rc;
-        XMB_HIP(b, hipMemcpyAsync(sl.h_status, sl.d_status, (size_t)n_all * 4, hipMemcpyDeviceToHost, st));
-        XMB_HIP(b, hipMemcpyAsync(sl.h_crc, sl.d_crc, (size_t)n_all * 4, hipMemcpyDeviceToHost, st));
+        XMF_HIP(b, hipMemcpyAsync(sl.h_status, sl.d_status, (size_t)n_all * 4, hipMemcpyDeviceToHost, st));
+        XMF_HIP(b, hipMemcpyAsync(sl.h_crc, sl.d_crc, (size_t)n_all * 4, hipMemcpyDeviceToHost, st));
     }
-    XMB_HIP(b, hipEventRecord(sl.ev[1], st));
+    XMF_HIP(b, hipEventRecord(sl.ev[1], st));
     // (what of the inflated window goes back for the writer is asked for afterwards: xm_bamdev_fetch_wanted / _fetch_raw)
     for (int f = 0; f < 2; ++f) {
         PerFile &q = sl.pf[f];
         const uint32_t n_seg = q.h_summary[8];
         const uint32_t *seg_at = q.h_seg;
-        XMB_HIP(b, hipMemsetAsync(q.d_summary, 0, 8 * sizeof(uint32_t), st));
+        XMF_HIP(b, hipMemsetAsync(q.d_summary, 0, 8 * sizeof(uint32_t), st));
         if (n_seg) {
             // counts, exits, record starts and fields of the blocks' segments came with the inflate launch; the pieces of the
             // carried tail (bytes of the previous window) are walked here
@@ -1407,13 +1429,11 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
                                                                                q.d_name_len, q.d_a, q.d_x, q.d_rflag, q.d_ncig, q.d_cig_at, rec_cap);
             }
         }
-        XMB_HIP(b, hipMemcpyAsync(q.h_summary, q.d_summary, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        XMF_HIP(b, hipMemcpyAsync(q.h_summary, q.d_summary, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
     t_issued = since();
-    XMB_HIP(b, hipEventRecord(sl.ev_wait, st));
-    XMB_HIP(b, hipEventSynchronize(sl.ev_wait));
+    XMF_TRY(wait_for(b, st, sl.ev_wait));
     t_sync1 = since();
-    if (hipGetLastError() != hipSuccess) return XM_ERR_HIP;
     // ---- what the device found ------------------------------------------------------------------------------------------
     uint64_t n_rec[2], stop[2];
     for (int f = 0; f < 2; ++f) {
@@ -1440,10 +1460,10 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
     uint64_t n = std::min(std::min(n_rec[0], n_rec[1]), max_records);
     const bool by_runs = skip && n > 0;                                    // the run kernels ran (a file without a record has no run either)
     // ---- strip + pair ------------------------------------------------------------------------------------------------------
-    XMB_HIP(b, hipEventRecord(sl.ev[1], st));
-    sl.h_state[0] = 0xFFFFFFFFu; sl.h_state[1] = 0; sl.h_state[2] = 0; sl.h_state[3] = 0xFFFFFFFFu;
-    sl.h_state[4] = sl.h_state[5] = sl.h_state[6] = sl.h_state[7] = 0;
-    XMB_HIP(b, hipMemcpyAsync(sl.d_state, sl.h_state, 8 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    XMF_HIP(b, hipEventRecord(sl.ev[1], st));
+    std::fill(sl.h_state, sl.h_state + BS_RUN_WORDS, 0u);
+    sl.h_state[BS_MISMATCH] = sl.h_state[BS_OPEN_RUN] = 0xFFFFFFFFu;
+    XMF_HIP(b, hipMemcpyAsync(sl.d_state, sl.h_state, BS_RUN_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     bool whole[2];
     for (int f = 0; f < 2; ++f) {
         PerFile &q = sl.pf[f];
@@ -1465,13 +1485,11 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
                                                                          tags, ro);
         }
         for (int f = 0; f < 2 && skip; ++f) {
-            // the run starts of the file's records, their fields next to each other; how many: d_state[4 + f]
+            // the run starts of the file's records, their fields next to each other; how many: state word BS_RUNS + f
             PerFile &q = sl.pf[f];
-            const uint32_t nf = (uint32_t)n_rec[f], n_part = (nf + SCAN_TILE - 1u) / SCAN_TILE;
+            const uint32_t nf = (uint32_t)n_rec[f];
             run_start_kernel<<<(nf + 255u) / 256u, 256, 0, st>>>(q.d_raw, q.d_name_off, q.d_name_len, q.d_rflag, nf, q.d_wsize, sl.d_state);
-            size_sum_kernel<<<n_part, 256, 0, st>>>(q.d_wsize, nf, q.d_part);
-            part_scan_kernel<<<1, 1024, 0, st>>>(q.d_part, n_part, sl.d_state + 4 + f);
-            size_place_kernel<false><<<n_part, 256, 0, st>>>(q.d_wsize, nf, q.d_part, q.d_place);
+            scan_sizes<false>(st, q.d_wsize, nf, q.d_part, q.d_place, sl.d_state + BS_RUNS + f);
             const RecCols from = {q.d_rec_off, q.d_name_off, q.d_name_len, q.d_a, q.d_x, q.d_rflag, cigar ? q.d_ncig : nullptr, cigar ? q.d_cig_at : nullptr};
             const RecCols to = {q.d_r_rec_off, q.d_r_name_off, q.d_r_name_len, q.d_r_a, q.d_r_x, q.d_r_flag, q.d_r_ncig, q.d_r_cig_at};
             run_select_kernel<<<(nf + 255u) / 256u, 256, 0, st>>>(from, q.d_place, nf, to);
@@ -1481,47 +1499,45 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
                                  : FileRecs{a.d_raw, a.d_name_off, a.d_name_len, a.d_a, a.d_x, a.d_rflag};
         const FileRecs f2 = skip ? FileRecs{c.d_raw, c.d_r_name_off, c.d_r_name_len, c.d_r_a, c.d_r_x, c.d_r_flag}
                                  : FileRecs{c.d_raw, c.d_name_off, c.d_name_len, c.d_a, c.d_x, c.d_rflag};
-        pair_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(f1, f2, (uint32_t)n, paired ? 1 : 0, skip ? sl.d_state + 4 : nullptr,
+        pair_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(f1, f2, (uint32_t)n, paired ? 1 : 0, skip ? sl.d_state + BS_RUNS : nullptr,
                                                                    (whole[0] ? 0u : 1u) | (whole[1] ? 0u : 2u), sl.d_col[0], sl.d_col[1], sl.d_col[2], sl.d_col[3],
                                                                    reinterpret_cast<unsigned long long *>(sl.d_bits), sl.pf[0].d_lflag, sl.pf[1].d_lflag, sl.d_state);
         for (int f = 0; f < 2; ++f) {
             PerFile &q = sl.pf[f];
-            XMB_HIP(b, hipMemcpyAsync(q.h_lflag, q.d_lflag, (size_t)n, hipMemcpyDeviceToHost, st));
+            XMF_HIP(b, hipMemcpyAsync(q.h_lflag, q.d_lflag, (size_t)n, hipMemcpyDeviceToHost, st));
             if (skip)                                                      // where the run starts' records begin: entry n too, when there is one
-                XMB_HIP(b, hipMemcpyAsync(q.h_pair_off, q.d_r_rec_off, (size_t)std::min<uint64_t>(n + 1, n_rec[f]) * 4, hipMemcpyDeviceToHost, st));
+                XMF_HIP(b, hipMemcpyAsync(q.h_pair_off, q.d_r_rec_off, (size_t)std::min<uint64_t>(n + 1, n_rec[f]) * 4, hipMemcpyDeviceToHost, st));
         }
     }
     for (int f = 0; f < 2; ++f)                                            // the whole record table: the writer prints from it, and the next
         if (n_rec[f])                                                      // window cuts its carried tail at boundaries it lists
-            XMB_HIP(b, hipMemcpyAsync(sl.pf[f].h_rec_off, sl.pf[f].d_rec_off, (size_t)n_rec[f] * 4, hipMemcpyDeviceToHost, st));
-    XMB_HIP(b, hipMemcpyAsync(sl.h_state, sl.d_state, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    XMB_HIP(b, hipEventRecord(sl.ev[2], st));
-    XMB_HIP(b, hipEventRecord(sl.ev_wait, st));
-    XMB_HIP(b, hipEventSynchronize(sl.ev_wait));
-    if (hipGetLastError() != hipSuccess) return XM_ERR_HIP;
+            XMF_HIP(b, hipMemcpyAsync(sl.pf[f].h_rec_off, sl.pf[f].d_rec_off, (size_t)n_rec[f] * 4, hipMemcpyDeviceToHost, st));
+    XMF_HIP(b, hipMemcpyAsync(sl.h_state, sl.d_state, BS_RUN_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    XMF_HIP(b, hipEventRecord(sl.ev[2], st));
+    XMF_TRY(wait_for(b, st, sl.ev_wait));
     (void)hipEventElapsedTime(&ms, sl.ev[1], sl.ev[2]);
     out->ms_kernels = ms;
-    if (sl.h_state[2] & 2u) { out->bad_block = 3; return XM_OK; }          // a malformed record
-    if (sl.h_state[2] & 1u) out->weird = 1;
+    if (sl.h_state[BS_WEIRD] & 2u) { out->bad_block = 3; return XM_OK; }          // a malformed record
+    if (sl.h_state[BS_WEIRD] & 1u) out->weird = 1;
     // what each file can pair: its records, or (the skipping walk) its runs
     uint64_t n_can[2] = {n_rec[0], n_rec[1]};
     if (by_runs) {
-        n_can[0] = sl.h_state[4]; n_can[1] = sl.h_state[5];
+        n_can[0] = sl.h_state[BS_RUNS]; n_can[1] = sl.h_state[BS_RUNS + 1];
         if (n_can[0] > n_rec[0] || n_can[1] > n_rec[1]) return XM_ERR_HIP;
         n = std::min(n, std::min(n_can[0], n_can[1]));
     }
     bool cut = false, open_run = false;
-    if (sl.h_state[0] != 0xFFFFFFFFu && sl.h_state[0] < n) {
-        out->mismatch_at = (int64_t)sl.h_state[0];
-        n = sl.h_state[0];                                                  // records at and behind it are not reported
+    if (sl.h_state[BS_MISMATCH] != 0xFFFFFFFFu && sl.h_state[BS_MISMATCH] < n) {
+        out->mismatch_at = (int64_t)sl.h_state[BS_MISMATCH];
+        n = sl.h_state[BS_MISMATCH];                                                 // records at and behind it are not reported
         cut = true;
     }
-    if (by_runs && sl.h_state[3] < n) {                                        // a run that may go on in the next window comes first
+    if (by_runs && sl.h_state[BS_OPEN_RUN] < n) {                                    // a run that may go on in the next window comes first
         out->mismatch_at = -1;
-        n = sl.h_state[3];
+        n = sl.h_state[BS_OPEN_RUN];
         cut = open_run = true;
     }
-    out->n_exceptions = sl.h_state[1];
+    out->n_exceptions = sl.h_state[BS_EXCEPTIONS];
     if (cut) {                                                              // the device counted the pairs behind the stop too
         uint64_t e = 0;
         for (uint64_t k = 0; k < n; ++k) e += ((sl.pf[0].h_lflag[k] | sl.pf[1].h_lflag[k]) & (XMS_LINE_EX_A | XMS_LINE_EX_X)) ? 1u : 0u;
@@ -1569,15 +1585,15 @@ int xm_bamdev_fetch_raw(xm_bamdev *b, int slot)
 {
     if (!b || slot < 0 || slot > 1) return XM_ERR_INVALID_ARG;
     Slot &sl = b->slot[slot];
-    XMB_HIP(b, hipSetDevice(b->device));
+    XMF_HIP(b, hipSetDevice(b->device));
     for (int f = 0; f < 2; ++f)                                             // the host copies of whole windows: only a slot that is asked has them
-        if (!sl.pf[f].h_raw) XMB_TRY(halloc(b, sl.pf[f].h_raw, (size_t)sl.raw_cap + 64));
-    XMB_HIP(b, hipEventRecord(sl.ev_inflated, sl.stream));
-    XMB_HIP(b, hipStreamWaitEvent(sl.copy_stream, sl.ev_inflated, 0));
+        if (!sl.pf[f].h_raw) XMF_TRY(halloc(b, sl.pf[f].h_raw, (size_t)sl.raw_cap + 64));
+    XMF_HIP(b, hipEventRecord(sl.ev_inflated, sl.stream));
+    XMF_HIP(b, hipStreamWaitEvent(sl.copy_stream, sl.ev_inflated, 0));
     for (int f = 0; f < 2; ++f)
         if (sl.pf[f].raw_len)
-            XMB_HIP(b, hipMemcpyAsync(sl.pf[f].h_raw, sl.pf[f].d_raw, (size_t)sl.pf[f].raw_len, hipMemcpyDeviceToHost, sl.copy_stream));
-    XMB_HIP(b, hipEventRecord(sl.ev_raw, sl.copy_stream));
+            XMF_HIP(b, hipMemcpyAsync(sl.pf[f].h_raw, sl.pf[f].d_raw, (size_t)sl.pf[f].raw_len, hipMemcpyDeviceToHost, sl.copy_stream));
+    XMF_HIP(b, hipEventRecord(sl.ev_raw, sl.copy_stream));
     sl.raw_issued = true;
     return XM_OK;
 }
@@ -1592,41 +1608,27 @@ int xm_bamdev_fetch_wanted(xm_bamdev *b, int slot, uint64_t n_records, int paire
 {
     if (!b || slot < 0 || slot > 1 || !out) return XM_ERR_INVALID_ARG;
     Slot &sl = b->slot[slot];
-    if (n_records > sl.record_cap || n_records > 0xFFFFFFF0ull || !sl.have_columns || !sl.classified) return XM_ERR_INVALID_ARG;
+    if (!sl.can_fetch(n_records)) return XM_ERR_INVALID_ARG;
     memset(out, 0, sizeof *out);
     out->raw1 = sl.pf[0].h_packed; out->raw2 = sl.pf[1].h_packed;
     out->off1 = sl.pf[0].h_place; out->off2 = sl.pf[1].h_place;
-    XMB_HIP(b, hipSetDevice(b->device));
+    XMF_HIP(b, hipSetDevice(b->device));
     hipStream_t st = sl.stream;
     const uint32_t n = (uint32_t)n_records;
+    uint64_t bytes[2] = {0, 0};
     if (n) {
-        const uint32_t n_part = (n + SCAN_TILE - 1u) / SCAN_TILE;
-        want_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, sl.d_bins4, n, paired ? 1 : 0,
-                                                       sink_mask, sl.pf[0].d_wsize, sl.pf[1].d_wsize);
+        launch_want(sl, n, paired, sink_mask);
         for (int f = 0; f < 2; ++f) {
             PerFile &q = sl.pf[f];
-            size_sum_kernel<<<n_part, 256, 0, st>>>(q.d_wsize, n, q.d_part);
-            part_scan_kernel<<<1, 1024, 0, st>>>(q.d_part, n_part, sl.d_state + 8 + f);
-            size_place_kernel<false><<<n_part, 256, 0, st>>>(q.d_wsize, n, q.d_part, q.d_place);
+            scan_sizes<false>(st, q.d_wsize, n, q.d_part, q.d_place, sl.d_state + BS_PACKED + f);
             pack_kernel<<<(n + 3u) / 4u, 256, 0, st>>>(q.d_raw, q.v_rec_off, q.d_wsize, q.d_place, n, q.d_packed);
         }
-        XMB_HIP(b, hipMemcpyAsync(sl.h_state + 8, sl.d_state + 8, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        XMB_HIP(b, hipEventRecord(sl.ev_wait, st));
-        XMB_HIP(b, hipEventSynchronize(sl.ev_wait));
-        if (hipGetLastError() != hipSuccess) return XM_ERR_HIP;
-        out->bytes1 = sl.h_state[8]; out->bytes2 = sl.h_state[9];
-        if (out->bytes1 > sl.raw_cap || out->bytes2 > sl.raw_cap) return XM_ERR_HIP;
+        XMF_HIP(b, hipMemcpyAsync(sl.h_state + BS_PACKED, sl.d_state + BS_PACKED, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        XMF_TRY(wait_for(b, st, sl.ev_wait));
+        out->bytes1 = bytes[0] = sl.h_state[BS_PACKED]; out->bytes2 = bytes[1] = sl.h_state[BS_PACKED + 1];
+        if (bytes[0] > sl.raw_cap || bytes[1] > sl.raw_cap) return XM_ERR_HIP;
     }
-    // the packed records and the table of where each went, on the copy stream (the kernels above have finished)
-    for (int f = 0; f < 2; ++f) {
-        PerFile &q = sl.pf[f];
-        const uint64_t bytes = f == 0 ? out->bytes1 : out->bytes2;
-        if (bytes) XMB_HIP(b, hipMemcpyAsync(q.h_packed, q.d_packed, (size_t)bytes, hipMemcpyDeviceToHost, sl.copy_stream));
-        if (n) XMB_HIP(b, hipMemcpyAsync(q.h_place, q.d_place, (size_t)n * 4, hipMemcpyDeviceToHost, sl.copy_stream));
-    }
-    XMB_HIP(b, hipEventRecord(sl.ev_raw, sl.copy_stream));
-    sl.raw_issued = true;
-    return XM_OK;
+    return files_home(b, sl, bytes, n, false);         // (the kernels above have finished)
 }
 
 int xm_bamdev_set_refs(xm_bamdev *b, int file, const uint8_t *names, const uint32_t *at, uint32_t n_refs)
@@ -1634,17 +1636,17 @@ int xm_bamdev_set_refs(xm_bamdev *b, int file, const uint8_t *names, const uint3
     if (!b || file < 0 || file > 1 || (n_refs && (!names || !at))) return XM_ERR_INVALID_ARG;
     for (uint32_t k = 0; k < n_refs; ++k)
         if (at[k + 1] < at[k]) return XM_ERR_INVALID_ARG;
-    XMB_HIP(b, hipSetDevice(b->device));
-    XMB_HIP(b, hipDeviceSynchronize());
+    XMF_HIP(b, hipSetDevice(b->device));
+    XMF_HIP(b, hipDeviceSynchronize());
     for (int slot = 0; slot < 2; ++slot) {                                  // a copy per slot: the slots' streams share nothing
         PerFile &q = b->slot[slot].pf[file];
         q.n_refs = 0;
         q.refs_set = false;
         const size_t bytes = n_refs ? at[n_refs] : 0;
-        XMB_TRY(dalloc(b, q.d_ref_names, bytes + 16)); XMB_TRY(dalloc(b, q.d_ref_at, (size_t)n_refs + 1));
+        XMF_TRY(dalloc(b, q.d_ref_names, bytes + 16)); XMF_TRY(dalloc(b, q.d_ref_at, (size_t)n_refs + 1));
         if (n_refs) {
-            if (bytes) XMB_HIP(b, hipMemcpy(q.d_ref_names, names, bytes, hipMemcpyHostToDevice));
-            XMB_HIP(b, hipMemcpy(q.d_ref_at, at, ((size_t)n_refs + 1) * 4, hipMemcpyHostToDevice));
+            if (bytes) XMF_HIP(b, hipMemcpy(q.d_ref_names, names, bytes, hipMemcpyHostToDevice));
+            XMF_HIP(b, hipMemcpy(q.d_ref_at, at, ((size_t)n_refs + 1) * 4, hipMemcpyHostToDevice));
         }
         q.n_refs = n_refs;
         q.refs_set = true;
@@ -1656,15 +1658,15 @@ int xm_bamdev_fetch_text(xm_bamdev *b, int slot, uint64_t n_records, int paired,
 {
     if (!b || slot < 0 || slot > 1 || !out) return XM_ERR_INVALID_ARG;
     Slot &sl = b->slot[slot];
-    if (n_records > sl.record_cap || n_records > 0xFFFFFFF0ull || !sl.have_columns || !sl.classified) return XM_ERR_INVALID_ARG;
+    if (!sl.can_fetch(n_records)) return XM_ERR_INVALID_ARG;
     if (!sl.pf[0].refs_set || !sl.pf[1].refs_set) return XM_ERR_INVALID_ARG;          // RNAME / RNEXT need xm_bamdev_set_refs
     memset(out, 0, sizeof *out);
-    XMB_HIP(b, hipSetDevice(b->device));
+    XMF_HIP(b, hipSetDevice(b->device));
     for (int f = 0; f < 2; ++f) {
         PerFile &q = sl.pf[f];
         if (q.llen_records < sl.record_cap) {
             q.llen_records = 0;
-            XMB_TRY(halloc(b, q.h_llen, (size_t)sl.record_cap + 64));
+            XMF_TRY(halloc(b, q.h_llen, (size_t)sl.record_cap + 64));
             q.llen_records = sl.record_cap;
         }
     }
@@ -1677,103 +1679,56 @@ int xm_bamdev_fetch_text(xm_bamdev *b, int slot, uint64_t n_records, int paired,
     // the line lengths are summed in 32 bits: a record's text is at most five times its bytes (xm_bam.cpp: a B:c element, 1 -> "-128,"),
     // so windows beyond 2^32 / 5 bytes are the host printer's
     if (sl.pf[0].raw_len > 0x30000000ull || sl.pf[1].raw_len > 0x30000000ull) { out->status = 2; return XM_OK; }
-    const uint32_t n_part = (n + SCAN_TILE - 1u) / SCAN_TILE;
     const uint32_t text_cap = (uint32_t)std::min<uint64_t>(sl.raw_cap, 0xFFFFFFF0ull);      // the packed-record buffers hold the text
-    XMB_HIP(b, hipMemsetAsync(sl.d_state + 13, 0, sizeof(uint32_t), st));
-    want_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, sl.d_bins4, n, paired ? 1 : 0,
-                                                   sink_mask, sl.pf[0].d_wsize, sl.pf[1].d_wsize);
+    XMF_HIP(b, hipMemsetAsync(sl.d_state + BS_GATHER + GS_FLAG, 0, sizeof(uint32_t), st));
+    launch_want(sl, n, paired, sink_mask);
     for (int f = 0; f < 2; ++f) {
         PerFile &q = sl.pf[f];
-        const RefTable refs = {q.d_ref_names, q.d_ref_at, q.n_refs};
-        text_size_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(q.d_raw, q.v_rec_off, n, refs, q.d_wsize, sl.d_state);
-        size_sum_kernel<<<n_part, 256, 0, st>>>(q.d_wsize, n, q.d_part);
-        part_scan_kernel<<<1, 1024, 0, st>>>(q.d_part, n_part, sl.d_state + 8 + f);
-        size_place_kernel<false><<<n_part, 256, 0, st>>>(q.d_wsize, n, q.d_part, q.d_place);
+        text_size_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(q.d_raw, q.v_rec_off, n, q.refs(), q.d_wsize, sl.d_state);
+        scan_sizes<false>(st, q.d_wsize, n, q.d_part, q.d_place, sl.d_state + BS_PACKED + f);
     }
-    XMB_HIP(b, hipMemcpyAsync(sl.h_state + 8, sl.d_state + 8, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    XMB_HIP(b, hipEventRecord(sl.ev_wait, st));
-    XMB_HIP(b, hipEventSynchronize(sl.ev_wait));
-    if (hipGetLastError() != hipSuccess) return XM_ERR_HIP;
-    out->bytes1 = sl.h_state[8]; out->bytes2 = sl.h_state[9];
-    if (sl.h_state[13] != 0u) { out->status = 1; return XM_OK; }            // a field the host prints (binary64)
-    if (out->bytes1 > text_cap || out->bytes2 > text_cap) { out->status = 2; return XM_OK; }     // more text than the buffers hold
+    // (the packed bytes, the CIGAR totals, the gather's pad and its flag: one copy)
+    XMF_HIP(b, hipMemcpyAsync(sl.h_state + BS_PACKED, sl.d_state + BS_PACKED, (BS_GATHER + GS_FLAG + 1 - BS_PACKED) * sizeof(uint32_t),
+                              hipMemcpyDeviceToHost, st));
+    XMF_TRY(wait_for(b, st, sl.ev_wait));
+    const uint64_t bytes[2] = {sl.h_state[BS_PACKED], sl.h_state[BS_PACKED + 1]};
+    out->bytes1 = bytes[0]; out->bytes2 = bytes[1];
+    if (sl.h_state[BS_GATHER + GS_FLAG] != 0u) { out->status = 1; return XM_OK; }            // a field the host prints (binary64)
+    if (bytes[0] > text_cap || bytes[1] > text_cap) { out->status = 2; return XM_OK; }     // more text than the buffers hold
     for (int f = 0; f < 2; ++f) {
         PerFile &q = sl.pf[f];
-        const RefTable refs = {q.d_ref_names, q.d_ref_at, q.n_refs};
-        text_fill_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(q.d_raw, q.v_rec_off, n, refs, q.d_wsize, q.d_place, q.d_packed, text_cap);
+        text_fill_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(q.d_raw, q.v_rec_off, n, q.refs(), q.d_wsize, q.d_place, q.d_packed, text_cap);
     }
     // the text and its line table, on the copy stream behind the kernels
-    XMB_HIP(b, hipEventRecord(sl.ev_inflated, st));
-    XMB_HIP(b, hipStreamWaitEvent(sl.copy_stream, sl.ev_inflated, 0));
-    for (int f = 0; f < 2; ++f) {
-        PerFile &q = sl.pf[f];
-        const uint64_t bytes = f == 0 ? out->bytes1 : out->bytes2;
-        if (bytes) XMB_HIP(b, hipMemcpyAsync(q.h_packed, q.d_packed, (size_t)bytes, hipMemcpyDeviceToHost, sl.copy_stream));
-        XMB_HIP(b, hipMemcpyAsync(q.h_place, q.d_place, (size_t)n * 4, hipMemcpyDeviceToHost, sl.copy_stream));
-        XMB_HIP(b, hipMemcpyAsync(q.h_llen, q.d_wsize, (size_t)n * 4, hipMemcpyDeviceToHost, sl.copy_stream));
-    }
-    XMB_HIP(b, hipEventRecord(sl.ev_raw, sl.copy_stream));
-    sl.raw_issued = true;
-    return XM_OK;
+    XMF_HIP(b, hipEventRecord(sl.ev_inflated, st));
+    XMF_HIP(b, hipStreamWaitEvent(sl.copy_stream, sl.ev_inflated, 0));
+    return files_home(b, sl, bytes, n, true);
 }
 
 int xm_bamdev_fetch_bins(xm_bamdev *b, int slot, uint64_t n_records, int paired, uint32_t sink_mask, xm_bamdev_bins *out)
 {
     if (!b || slot < 0 || slot > 1 || !out) return XM_ERR_INVALID_ARG;
     Slot &sl = b->slot[slot];
-    if (n_records > sl.record_cap || n_records > 0xFFFFFFF0ull || !sl.have_columns || !sl.classified) return XM_ERR_INVALID_ARG;
+    if (!sl.can_fetch(n_records)) return XM_ERR_INVALID_ARG;
     if (!sl.pf[0].refs_set || !sl.pf[1].refs_set) return XM_ERR_INVALID_ARG;          // RNAME / RNEXT need xm_bamdev_set_refs
-    memset(out, 0, sizeof *out);
-    out->text = sl.h_packed_all;
-    const uint32_t n = (uint32_t)n_records;
-    const uint64_t units64 = sl.h_off_counts[7];                                    // of the slot's last xm_bamdev_classify
-    if (n == 0 || units64 == 0) return XM_OK;
-    if (units64 > n_records) return XM_ERR_INVALID_ARG;
-    const uint32_t n_units = (uint32_t)units64;
-    XMB_HIP(b, hipSetDevice(b->device));
+    BinsJob job;
+    XMF_TRY(begin_bins(b, sl, n_records, paired, sink_mask, true, out, job));
+    if (job.n_units == 0) return XM_OK;
     hipStream_t st = sl.stream;
-    // line lengths and the places of the units are summed in 32 bits (as in xm_bamdev_fetch_text)
-    if (sl.pf[0].raw_len > 0x30000000ull || sl.pf[1].raw_len > 0x30000000ull) { out->status = 2; return XM_OK; }
-    const uint64_t out_cap = std::min<uint64_t>(2 * sl.packed_stride - 64u, 0xFFFFFFF0ull);
-    const uint32_t n_part = (n_units + SCAN_TILE - 1u) / SCAN_TILE;
-    const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(sl.d_off_counts);
-    XMB_HIP(b, hipMemsetAsync(sl.d_state + 13, 0, 13 * sizeof(uint32_t), st));
-    want_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, sl.d_bins4, n, paired ? 1 : 0,
-                                                   sink_mask, sl.pf[0].d_wsize, sl.pf[1].d_wsize);
-    RefTable refs[2];
+    const uint32_t n = job.n, n_units = job.n_units;
     for (int f = 0; f < 2; ++f) {
-        PerFile &q = sl.pf[f];
-        refs[f] = RefTable{q.d_ref_names, q.d_ref_at, q.n_refs};
-        text_size_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(q.d_raw, q.v_rec_off, n, refs[f], q.d_wsize, sl.d_state);
+        const PerFile &q = sl.pf[f];
+        text_size_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(q.d_raw, q.v_rec_off, n, q.refs(), q.d_wsize, sl.d_state);
     }
-    unit_size_kernel<<<(n_units + 255u) / 256u, 256, 0, st>>>(sl.d_idx, d_off, n_units, n, paired ? 1 : 0, sink_mask, sl.pf[0].d_wsize, sl.pf[1].d_wsize,
-                                                             sl.d_usize, reinterpret_cast<unsigned long long *>(sl.d_state + 24));
-    size_sum_kernel<<<n_part, 256, 0, st>>>(sl.d_usize, n_units, sl.d_upart);
-    part_scan_kernel<<<1, 1024, 0, st>>>(sl.d_upart, n_part, sl.d_state + 14);
-    size_place_kernel<true><<<n_part, 256, 0, st>>>(sl.d_usize, n_units, sl.d_upart, sl.d_uplace);
-    // where each bin's text begins: the place of its first unit (state[16..23]; [14] the total, [13] the printer's flag)
-    bin_start_kernel<<<1, 64, 0, st>>>(sl.d_uplace, d_off, n_units, sl.d_state + 14, sl.d_state + 16);
-    XMB_HIP(b, hipMemcpyAsync(sl.h_state + 13, sl.d_state + 13, 13 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    XMB_HIP(b, hipEventRecord(sl.ev_wait, st));
-    XMB_HIP(b, hipEventSynchronize(sl.ev_wait));
-    if (hipGetLastError() != hipSuccess) return XM_ERR_HIP;
-    if (sl.h_state[13] != 0u) { out->status = 1; return XM_OK; }            // a field the host prints (binary64)
-    uint64_t total = 0;
-    memcpy(&total, sl.h_state + 24, sizeof total);                          // summed in 64 bits: the 32-bit places hold only if this fits
-    if (total > out_cap) { out->status = 2; return XM_OK; }                 // more text than the buffers hold
-    for (int k = 0; k < 8; ++k) out->bin_off[k] = sl.h_state[16 + k];
+    Placed at;
+    XMF_TRY(place_bins(b, sl, job, paired, sink_mask, at));
+    if (at.flag != 0u) { out->status = 1; return XM_OK; }                   // a field the host prints (binary64)
+    if (at.total > job.out_cap) { out->status = 2; return XM_OK; }          // more text than the buffers hold
+    for (int k = 0; k < 8; ++k) out->bin_off[k] = at.starts[k];
     line_fill_kernel<<<((paired ? 2u : 1u) * n_units + 255u) / 256u, 256, 0, st>>>(
-        sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, refs[0], refs[1], sl.d_idx, d_off, n_units, n, paired ? 1 : 0, sink_mask,
-        sl.pf[0].d_wsize, sl.pf[1].d_wsize, sl.d_usize, sl.d_uplace, sl.d_packed_all, (uint32_t)out_cap, WIDE_MIN);
-    // the stream goes to the host on the copy stream behind the kernels (beside the next window's inflate launch on the other slot)
-    XMB_HIP(b, hipEventRecord(sl.ev_inflated, st));
-    sl.fill_issued = true;
-    XMB_HIP(b, hipStreamWaitEvent(sl.copy_stream, sl.ev_inflated, 0));
-    out_copy(sl.d_packed_all, sl.h_packed_all, total, sl.copy_stream);      // (the buffers end 64 bytes behind out_cap)
-    XMB_HIP(b, hipEventRecord(sl.ev_raw, sl.copy_stream));
-    sl.raw_issued = true;
-    if (hipGetLastError() != hipSuccess) return XM_ERR_HIP;
-    return XM_OK;
+        sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, sl.pf[0].refs(), sl.pf[1].refs(), sl.d_idx, job.d_off, n_units, n, paired ? 1 : 0, sink_mask,
+        sl.pf[0].d_wsize, sl.pf[1].d_wsize, sl.d_usize, sl.d_uplace, sl.d_packed_all, (uint32_t)job.out_cap, WIDE_MIN);
+    return bins_home(b, sl, at.total);
 }
 
 int xm_bamdev_fetch_bins_bam(xm_bamdev *b, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload,
@@ -1781,75 +1736,45 @@ int xm_bamdev_fetch_bins_bam(xm_bamdev *b, int slot, uint64_t n_records, int pai
 {
     if (!b || slot < 0 || slot > 1 || !out) return XM_ERR_INVALID_ARG;
     Slot &sl = b->slot[slot];
-    if (n_records > sl.record_cap || n_records > 0xFFFFFFF0ull || !sl.have_columns || !sl.classified) return XM_ERR_INVALID_ARG;
+    if (!sl.can_fetch(n_records)) return XM_ERR_INVALID_ARG;
     const uint32_t P = block_payload ? block_payload : 65280u;
     if (P < 64u || P > 65280u) return XM_ERR_INVALID_ARG;
-    memset(out, 0, sizeof *out);
-    out->text = sl.h_packed_all;
-    const uint32_t n = (uint32_t)n_records;
-    const uint64_t units64 = sl.h_off_counts[7];                                    // of the slot's last xm_bamdev_classify
-    if (n == 0 || units64 == 0) return XM_OK;
-    if (units64 > n_records) return XM_ERR_INVALID_ARG;
-    const uint32_t n_units = (uint32_t)units64;
-    XMB_HIP(b, hipSetDevice(b->device));
+    BinsJob job;                                       // (W1 notes 4 + block_size of every record a sink takes: the bytes it has in a BAM file)
+    XMF_TRY(begin_bins(b, sl, n_records, paired, sink_mask, false, out, job));
+    if (job.n_units == 0) return XM_OK;
     hipStream_t st = sl.stream;
-    const uint64_t out_cap = std::min<uint64_t>(2 * sl.packed_stride - 64u, 0xFFFFFFF0ull);
-    const uint32_t n_part = (n_units + SCAN_TILE - 1u) / SCAN_TILE;
-    const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(sl.d_off_counts);
-    XMB_HIP(b, hipMemsetAsync(sl.d_state + 13, 0, 13 * sizeof(uint32_t), st));
-    // W1 notes 4 + block_size of every record a sink takes: the bytes it has in a BAM file
-    want_kernel<<<(n + 255u) / 256u, 256, 0, st>>>(sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, sl.d_bins4, n, paired ? 1 : 0,
-                                                   sink_mask, sl.pf[0].d_wsize, sl.pf[1].d_wsize);
-    unit_size_kernel<<<(n_units + 255u) / 256u, 256, 0, st>>>(sl.d_idx, d_off, n_units, n, paired ? 1 : 0, sink_mask, sl.pf[0].d_wsize, sl.pf[1].d_wsize,
-                                                             sl.d_usize, reinterpret_cast<unsigned long long *>(sl.d_state + 24));
-    size_sum_kernel<<<n_part, 256, 0, st>>>(sl.d_usize, n_units, sl.d_upart);
-    part_scan_kernel<<<1, 1024, 0, st>>>(sl.d_upart, n_part, sl.d_state + 14);
-    size_place_kernel<true><<<n_part, 256, 0, st>>>(sl.d_usize, n_units, sl.d_upart, sl.d_uplace);
-    // where each bin's payload begins (state[16..23]; [14] the total)
-    bin_start_kernel<<<1, 64, 0, st>>>(sl.d_uplace, d_off, n_units, sl.d_state + 14, sl.d_state + 16);
-    XMB_HIP(b, hipMemcpyAsync(sl.h_state + 13, sl.d_state + 13, 13 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    XMB_HIP(b, hipEventRecord(sl.ev_wait, st));
-    XMB_HIP(b, hipEventSynchronize(sl.ev_wait));
-    if (hipGetLastError() != hipSuccess) return XM_ERR_HIP;
-    uint64_t total = 0;
-    memcpy(&total, sl.h_state + 24, sizeof total);                          // summed in 64 bits: the 32-bit places hold only if this fits
-    if (total > out_cap) { out->status = 2; return XM_OK; }
+    const uint32_t n = job.n, n_units = job.n_units;
+    Placed at;
+    XMF_TRY(place_bins(b, sl, job, paired, sink_mask, at));
+    if (at.total > job.out_cap) { out->status = 2; return XM_OK; }
     // the framed layout, as O1 derives it on the device: the same sums in 64 bits, against the same capacity, before anything is written
     uint64_t framed = 0, n_members = 0;
     for (int k = 0; k < 7; ++k) {
         out->bin_off[k] = framed;
-        if (sl.h_state[17 + k] < sl.h_state[16 + k]) return XM_ERR_HIP;
-        const uint64_t len = sl.h_state[17 + k] - sl.h_state[16 + k], members = (len + P - 1u) / P;
+        if (at.starts[k + 1] < at.starts[k]) return XM_ERR_HIP;
+        const uint64_t len = at.starts[k + 1] - at.starts[k], members = (len + P - 1u) / P;
         framed += len + members * BGZF_FRAME;
         n_members += members;
     }
     out->bin_off[7] = framed;
-    if (framed > out_cap) { memset(out->bin_off, 0, sizeof out->bin_off); out->status = 2; return XM_OK; }
+    if (framed > job.out_cap) { memset(out->bin_off, 0, sizeof out->bin_off); out->status = 2; return XM_OK; }
     if (n_members == 0) return XM_OK;
     if (n_members > sl.member_cap) {                                        // (the slot's stream is idle: the wait above)
         sl.member_cap = 0;
         const size_t cap = (size_t)n_members + (size_t)n_members / 4 + 64;
-        XMB_TRY(dalloc(b, sl.d_members, cap)); XMB_TRY(dalloc(b, sl.d_member_crc, cap));
-        if (!sl.d_layout) XMB_TRY(dalloc(b, sl.d_layout, 1));
+        XMF_TRY(dalloc(b, sl.d_members, cap)); XMF_TRY(dalloc(b, sl.d_member_crc, cap));
+        if (!sl.d_layout) XMF_TRY(dalloc(b, sl.d_layout, 1));
         sl.member_cap = cap;
     }
     const uint32_t nm = (uint32_t)n_members;
-    bam_layout_kernel<<<(nm + 255u) / 256u, 256, 0, st>>>(sl.d_state + 16, P, nm, sl.d_layout, sl.d_members);
+    bam_layout_kernel<<<(nm + 255u) / 256u, 256, 0, st>>>(job.gs + GS_STARTS, P, nm, sl.d_layout, sl.d_members);
     record_fill_kernel<<<((paired ? 2u : 1u) * n_units + 3u) / 4u, 256, 0, st>>>(
-        sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, sl.d_idx, d_off, n_units, n, paired ? 1 : 0, sink_mask,
-        sl.pf[0].d_wsize, sl.pf[1].d_wsize, sl.d_usize, sl.d_uplace, sl.d_state + 16, sl.d_layout, P, ref_shift, sl.d_packed_all, (uint32_t)out_cap);
+        sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, sl.d_idx, job.d_off, n_units, n, paired ? 1 : 0, sink_mask,
+        sl.pf[0].d_wsize, sl.pf[1].d_wsize, sl.d_usize, sl.d_uplace, job.gs + GS_STARTS, sl.d_layout, P, ref_shift, sl.d_packed_all, (uint32_t)job.out_cap);
     const int rc = xm_bgzf_crc32_dev(b->ctx, st, sl.d_packed_all, sl.d_members, n_members, sl.d_member_crc);
     if (rc != XM_OK) return rc;
-    bam_frame_kernel<<<(nm + 255u) / 256u, 256, 0, st>>>(sl.d_members, sl.d_member_crc, nm, sl.d_packed_all, (uint32_t)out_cap);
-    // the stream goes to the host on the copy stream behind the kernels (beside the next window's inflate launch on the other slot)
-    XMB_HIP(b, hipEventRecord(sl.ev_inflated, st));
-    sl.fill_issued = true;
-    XMB_HIP(b, hipStreamWaitEvent(sl.copy_stream, sl.ev_inflated, 0));
-    out_copy(sl.d_packed_all, sl.h_packed_all, framed, sl.copy_stream);     // (the buffers end 64 bytes behind out_cap)
-    XMB_HIP(b, hipEventRecord(sl.ev_raw, sl.copy_stream));
-    sl.raw_issued = true;
-    if (hipGetLastError() != hipSuccess) return XM_ERR_HIP;
-    return XM_OK;
+    bam_frame_kernel<<<(nm + 255u) / 256u, 256, 0, st>>>(sl.d_members, sl.d_member_crc, nm, sl.d_packed_all, (uint32_t)job.out_cap);
+    return bins_home(b, sl, framed);
 }
 
 int xm_bamdev_raw_wait(xm_bamdev *b, int slot)
@@ -1857,8 +1782,8 @@ int xm_bamdev_raw_wait(xm_bamdev *b, int slot)
     if (!b || slot < 0 || slot > 1) return XM_ERR_INVALID_ARG;
     Slot &sl = b->slot[slot];
     if (!sl.raw_issued) return XM_OK;
-    XMB_HIP(b, hipSetDevice(b->device));
-    XMB_HIP(b, hipEventSynchronize(sl.ev_raw));
+    XMF_HIP(b, hipSetDevice(b->device));
+    XMF_HIP(b, hipEventSynchronize(sl.ev_raw));
     return XM_OK;
 }
 
@@ -1872,43 +1797,14 @@ int xm_bamdev_classify(xm_bamdev *b, int slot, int mode, uint64_t n_records, int
     *idx = sl.h_idx;
     memset(bin_offsets, 0, 8 * sizeof(uint64_t));
     memset(counts, 0, 64 * sizeof(uint64_t));
-    if (n_records == 0) { sl.classified = true; return XM_OK; }
-    XMB_HIP(b, hipSetDevice(b->device));
-    hipStream_t st = sl.stream;
+    if (n_records == 0) { sl.classified = true; return XM_OK; }      // (an empty window counts as classified: a fetch then returns nothing)
+    XMF_HIP(b, hipSetDevice(b->device));
     const bool cigar = sl.last_score_mode == XMS_SCORE_CIGAR;
-    int rc;
-    if (cigar) {
-        // the records' CIGAR words as packed CIGAR columns (col 0 / 2 hold NM), then the kernel that makes AS of them
-        for (int f = 0; f < 2; ++f) XMB_TRY(pack_cigar(sl, f, (uint32_t)n_records));
-        XMB_HIP(b, hipMemsetAsync(sl.d_state + 12, 0, sizeof(uint32_t), st));
-        const PerFile &a = sl.pf[0], &c = sl.pf[1];
-        rc = xm_classify_compact_cigar_packed_dev(b->ctx, st, mode, n_records, sl.d_col[0], a.d_cig_cnt, a.d_cig_tile, a.d_cig_ops, sl.d_col[1],
-                                                  sl.d_col[2], c.d_cig_cnt, c.d_cig_tile, c.d_cig_ops, sl.d_col[3], sl.d_bits, min_score_floor,
-                                                  sl.d_code, sl.d_bins4, sl.d_state + 12, sl.d_idx, sl.d_off_counts, sl.d_off_counts + 8);
-    } else {
-        rc = xm_classify_compact_dev(b->ctx, st, mode, n_records, sl.d_col[0], sl.d_col[1], sl.d_col[2], sl.d_col[3], sl.d_bits,
-                                     min_score_floor, sl.d_code, sl.d_bins4, sl.d_idx, sl.d_off_counts, sl.d_off_counts + 8);
-    }
-    if (rc != XM_OK) {
-        std::lock_guard<std::mutex> hold(b->error_lock);
-        b->last_error = xm_last_hip_error(b->ctx);
-        return rc;
-    }
-    XMB_HIP(b, hipMemcpyAsync(sl.h_code, sl.d_code, n_records, hipMemcpyDeviceToHost, st));
-    XMB_HIP(b, hipMemcpyAsync(sl.h_off_counts, sl.d_off_counts, 72 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (cigar) XMB_HIP(b, hipMemcpyAsync(sl.h_state + 12, sl.d_state + 12, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    XMB_HIP(b, hipStreamSynchronize(st));
-    if (cigar && sl.h_state[12] != 0u) return XM_ERR_RANGE;               // a score left int32: the caller's text rules decide
-    const uint64_t units = sl.h_off_counts[7];
-    if (units > n_records) return XM_ERR_HIP;
-    if (units) {
-        XMB_HIP(b, hipMemcpyAsync(sl.h_idx, sl.d_idx, units * 4, hipMemcpyDeviceToHost, st));
-        XMB_HIP(b, hipStreamSynchronize(st));
-    }
-    memcpy(bin_offsets, sl.h_off_counts, 8 * sizeof(uint64_t));
-    memcpy(counts, sl.h_off_counts + 8, 64 * sizeof(uint64_t));
-    sl.classified = true;
-    return XM_OK;
+    // the records' CIGAR words as packed CIGAR columns (col 0 / 2 hold NM), then the kernel that makes AS of them
+    for (int f = 0; f < 2 && cigar; ++f) XMF_TRY(pack_cigar(sl, f, (uint32_t)n_records));
+    const PerFile &a = sl.pf[0], &c = sl.pf[1];
+    const CigCols cig[2] = {{sl.d_col[0], a.d_cig_cnt, a.d_cig_tile, a.d_cig_ops}, {sl.d_col[2], c.d_cig_cnt, c.d_cig_tile, c.d_cig_ops}};
+    return sl.run_fused(b, sl.stream, mode, n_records, min_score_floor, cigar ? cig : nullptr, bin_offsets, counts);
 }
 
 int xm_bamdev_columns(xm_bamdev *b, int slot, uint64_t n_records, int32_t *as1, int32_t *xs1, int32_t *as2, int32_t *xs2,
@@ -1918,13 +1814,8 @@ int xm_bamdev_columns(xm_bamdev *b, int slot, uint64_t n_records, int32_t *as1, 
     Slot &sl = b->slot[slot];
     if (n_records > sl.record_cap || !sl.have_columns) return XM_ERR_INVALID_ARG;
     if (n_records == 0) return XM_OK;
-    XMB_HIP(b, hipSetDevice(b->device));
-    int32_t *dst[4] = {as1, xs1, as2, xs2};
-    for (int c = 0; c < 4; ++c)
-        if (dst[c]) XMB_HIP(b, hipMemcpyAsync(dst[c], sl.d_col[c], n_records * 4, hipMemcpyDeviceToHost, sl.stream));
-    if (unit_bits) XMB_HIP(b, hipMemcpyAsync(unit_bits, sl.d_bits, (n_records + 63) / 64 * 8, hipMemcpyDeviceToHost, sl.stream));
-    XMB_HIP(b, hipStreamSynchronize(sl.stream));
-    return XM_OK;
+    XMF_HIP(b, hipSetDevice(b->device));
+    return sl.columns_to_host(b, sl.stream, n_records, as1, xs1, as2, xs2, unit_bits);
 }
 
 int xm_bamdev_cigar_columns(xm_bamdev *b, int slot, int file, uint64_t n_records, int32_t *nm, uint8_t *cig_cnt, uint32_t *cig_tile,
@@ -1935,34 +1826,25 @@ int xm_bamdev_cigar_columns(xm_bamdev *b, int slot, int file, uint64_t n_records
     if (n_records > sl.record_cap || !sl.have_columns || sl.last_score_mode != XMS_SCORE_CIGAR) return XM_ERR_INVALID_ARG;
     *n_ops = 0;
     if (n_records == 0) { if (cig_tile) cig_tile[0] = 0; return XM_OK; }
-    XMB_HIP(b, hipSetDevice(b->device));
+    XMF_HIP(b, hipSetDevice(b->device));
     hipStream_t st = sl.stream;
     const PerFile &q = sl.pf[file];
-    XMB_TRY(pack_cigar(sl, file, (uint32_t)n_records));
-    XMB_HIP(b, hipMemcpyAsync(sl.h_state + 10 + file, sl.d_state + 10 + file, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (nm) XMB_HIP(b, hipMemcpyAsync(nm, sl.d_col[2 * file], n_records * 4, hipMemcpyDeviceToHost, st));
-    if (cig_cnt) XMB_HIP(b, hipMemcpyAsync(cig_cnt, q.d_cig_cnt, n_records, hipMemcpyDeviceToHost, st));
-    if (cig_tile) XMB_HIP(b, hipMemcpyAsync(cig_tile, q.d_cig_tile, (XM_CIG_TILES(n_records) + 1) * 4, hipMemcpyDeviceToHost, st));
-    XMB_HIP(b, hipStreamSynchronize(st));
-    *n_ops = sl.h_state[10 + file];
+    XMF_TRY(pack_cigar(sl, file, (uint32_t)n_records));
+    XMF_HIP(b, hipMemcpyAsync(sl.h_state + BS_CIG_OPS + file, sl.d_state + BS_CIG_OPS + file, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (nm) XMF_HIP(b, hipMemcpyAsync(nm, sl.d_col[2 * file], n_records * 4, hipMemcpyDeviceToHost, st));
+    if (cig_cnt) XMF_HIP(b, hipMemcpyAsync(cig_cnt, q.d_cig_cnt, n_records, hipMemcpyDeviceToHost, st));
+    if (cig_tile) XMF_HIP(b, hipMemcpyAsync(cig_tile, q.d_cig_tile, (XM_CIG_TILES(n_records) + 1) * 4, hipMemcpyDeviceToHost, st));
+    XMF_HIP(b, hipStreamSynchronize(st));
+    *n_ops = sl.h_state[BS_CIG_OPS + file];
     if (*n_ops > q.ops_cap) return XM_ERR_HIP;
     if (cig_ops) {
         if (ops_capacity < *n_ops) return XM_ERR_INVALID_ARG;
-        if (*n_ops) XMB_HIP(b, hipMemcpyAsync(cig_ops, q.d_cig_ops, *n_ops * 4, hipMemcpyDeviceToHost, st));
-        XMB_HIP(b, hipStreamSynchronize(st));
+        if (*n_ops) XMF_HIP(b, hipMemcpyAsync(cig_ops, q.d_cig_ops, *n_ops * 4, hipMemcpyDeviceToHost, st));
+        XMF_HIP(b, hipStreamSynchronize(st));
     }
     return XM_OK;
 }
 
-const char *xm_bamdev_last_error(const xm_bamdev *b)
-{
-    static thread_local std::string mine;
-    if (!b) return "";
-    {
-        std::lock_guard<std::mutex> hold(const_cast<xm_bamdev *>(b)->error_lock);
-        mine = b->last_error;
-    }
-    return mine.c_str();
-}
+const char *xm_bamdev_last_error(const xm_bamdev *b) { return last_error_text(b); }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // SURVEY f-2's gather kernel): which file a bin prints from, the bin of a place in the packed unit list, the size scan (three small
 // launches over a uint32 array), where each bin's text begins, and the copy of the finished stream into the host's page-locked,
 // device-mapped buffer.  Every kernel lives in an anonymous namespace: each translation unit that includes this gets its own.
+// The host code that drives them, the same for both front ends, is xm_slot.h; the gather's state words are named there (GS_*).
 #pragma once
 #include <chrono>
 #include <hip/hip_runtime.h>

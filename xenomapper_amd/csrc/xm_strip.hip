@@ -29,14 +29,10 @@
 
 #include <algorithm>
 #include <climits>
-#include <cstdio>
 #include <cstring>
-#include <mutex>
 #include <new>
-#include <string>
 
-#include "xm_gather.h"
-#include "xm_pinned.h"
+#include "xm_slot.h"
 
 namespace {
 
@@ -865,26 +861,20 @@ struct PerFile {
     uint64_t ops_cap = 0;
 };
 
-struct Slot {
+struct Slot : ClassifyOut, GatherPlan {               // (xm_slot.h: the columns and the classify outputs; the gather's per-unit arrays)
     uint64_t window_cap = 0, record_cap = 0;
     bool cigar_ready = false;                          // the CIGAR-only arrays exist for the current capacities
     PerFile pf[2];
-    int32_t *d_col[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t *d_bits = nullptr;
-    // classify outputs
-    uint8_t *d_code = nullptr, *d_bins4 = nullptr, *h_code = nullptr;
-    uint32_t *d_idx = nullptr, *h_idx = nullptr, *d_range = nullptr;
-    uint64_t *d_off_counts = nullptr, *h_off_counts = nullptr;     // 8 + 64 words (+ the range flag's word on the host side)
     uint32_t *d_state = nullptr;
     uint64_t *d_summary = nullptr, *h_summary = nullptr;
-    // xm_strip_fetch_bins: per unit the bytes of its lines and where they go, the six outputs as one stream on the device and in
-    // page-locked host memory, a few words of state; its copy to the host runs on a stream of its own
-    uint32_t *d_usize = nullptr, *d_uplace = nullptr, *d_upart = nullptr, *d_gstate = nullptr, *h_gstate = nullptr;
+    // xm_strip_fetch_bins: the six outputs as one stream on the device and in page-locked host memory, the gather's state block
+    // (xm_slot.h; GS_FLAG: a wanted line that is not '\t'.join(fields) as it stands); its copy to the host runs on a stream of its own
+    uint32_t *d_gstate = nullptr, *h_gstate = nullptr;
     uint8_t *d_out = nullptr, *h_out = nullptr;
-    uint64_t out_cap = 0, out_records = 0;
+    uint64_t out_cap = 0;
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_filled = nullptr, ev_out = nullptr;
-    bool out_issued = false, classified = false;
+    bool out_issued = false;
     hipStream_t stream = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     uint64_t uploaded[2] = {0, 0};                     // bytes of the staged windows already on their way (xm_strip_upload)
@@ -896,55 +886,11 @@ struct Slot {
 
 }  // namespace
 
-struct xm_strip {
-    xm_ctx *ctx = nullptr;
-    int device = 0;
+struct xm_strip : FrontEnd {
     Slot slot[XMS_SLOTS];
-    std::mutex error_lock;                             // the two slots are driven by two threads
-    std::string last_error;
 };
 
 namespace {
-
-int fail(xm_strip *s, hipError_t e, const char *what)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    if (s) {
-        std::lock_guard<std::mutex> hold(s->error_lock);
-        s->last_error = buf;
-    }
-    (void)hipGetLastError();        // reported here: a later launch check on this thread must not find it again
-    return e == hipErrorOutOfMemory ? XM_ERR_OOM : XM_ERR_HIP;
-}
-
-#define XMS_HIP(s, call)                                   \
-    do {                                                   \
-        hipError_t e_ = (call);                            \
-        if (e_ != hipSuccess) return fail((s), e_, #call); \
-    } while (0)
-
-#define XMS_TRY(expr)                  \
-    do {                               \
-        int rc_ = (expr);              \
-        if (rc_ != XM_OK) return rc_;  \
-    } while (0)
-
-template <typename T> void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
-template <typename T> void hfree(T *&p) { if (p) { (void)xmpin::host_free(p); p = nullptr; } }
-
-template <typename T> int dalloc(xm_strip *s, T *&p, size_t count)
-{
-    dfree(p);
-    XMS_HIP(s, hipMalloc((void **)&p, std::max<size_t>(count, 16) * sizeof(T)));
-    return XM_OK;
-}
-template <typename T> int halloc(xm_strip *s, T *&p, size_t count)
-{
-    hfree(p);
-    XMS_HIP(s, xmpin::host_malloc((void **)&p, std::max<size_t>(count, 16) * sizeof(T)));
-    return XM_OK;
-}
 
 void free_slot(Slot &sl)
 {
@@ -960,11 +906,10 @@ void free_slot(Slot &sl)
         dfree(q.d_nm); dfree(q.d_cpos); dfree(q.d_cig_tile); dfree(q.d_cig_ops); dfree(q.d_cig_cnt);
         q.ops_cap = 0;
     }
-    for (int c = 0; c < 4; ++c) dfree(sl.d_col[c]);
-    dfree(sl.d_bits); dfree(sl.d_code); dfree(sl.d_bins4); dfree(sl.d_idx);
-    hfree(sl.h_code); hfree(sl.h_idx);
-    dfree(sl.d_usize); dfree(sl.d_uplace); dfree(sl.d_upart); dfree(sl.d_out); hfree(sl.h_out);
-    sl.out_cap = sl.out_records = 0;
+    sl.release();
+    sl.free_units();
+    dfree(sl.d_out); hfree(sl.h_out);
+    sl.out_cap = 0;
     sl.window_cap = sl.record_cap = 0;
     sl.cigar_ready = false;
 }
@@ -978,11 +923,11 @@ int grow_window(xm_strip *s, Slot &sl, uint64_t bytes)
     sl.cigar_ready = false;
     for (int f = 0; f < 2; ++f) {
         PerFile &q = sl.pf[f];
-        XMS_TRY(halloc(s, q.h_text, (size_t)cap + 64));
-        XMS_TRY(dalloc(s, q.d_text, (size_t)cap + 256));              // S1 / S4 read whole 16-byte words / load steps
-        XMS_TRY(dalloc(s, q.d_mask, (size_t)cap / 16 + 16));
-        XMS_TRY(dalloc(s, q.d_chunk_cnt, n_chunks * WAVES));
-        XMS_TRY(dalloc(s, q.d_chunk_base, n_chunks * WAVES));
+        XMF_TRY(halloc(s, q.h_text, (size_t)cap + 64));
+        XMF_TRY(dalloc(s, q.d_text, (size_t)cap + 256));              // S1 / S4 read whole 16-byte words / load steps
+        XMF_TRY(dalloc(s, q.d_mask, (size_t)cap / 16 + 16));
+        XMF_TRY(dalloc(s, q.d_chunk_cnt, n_chunks * WAVES));
+        XMF_TRY(dalloc(s, q.d_chunk_base, n_chunks * WAVES));
     }
     sl.window_cap = cap;
     return XM_OK;
@@ -996,20 +941,14 @@ int grow_records(xm_strip *s, Slot &sl, uint64_t records)
     sl.cigar_ready = false;
     for (int f = 0; f < 2; ++f) {
         PerFile &q = sl.pf[f];
-        XMS_TRY(dalloc(s, q.d_lend, lines)); XMS_TRY(dalloc(s, q.d_lnext, lines));
-        XMS_TRY(dalloc(s, q.d_r_name_off, lines)); XMS_TRY(dalloc(s, q.d_r_name_len, lines)); XMS_TRY(dalloc(s, q.d_r_norm, lines));
-        XMS_TRY(dalloc(s, q.d_r_a, lines)); XMS_TRY(dalloc(s, q.d_r_x, lines)); XMS_TRY(dalloc(s, q.d_r_flag, lines + 64));
-        XMS_TRY(dalloc(s, q.d_blk_cnt, lines / SB + 2)); XMS_TRY(dalloc(s, q.d_blk_base, lines / SB + 2)); XMS_TRY(dalloc(s, q.d_sel, lines));
-        XMS_TRY(dalloc(s, q.d_loff, n)); XMS_TRY(dalloc(s, q.d_llen, n)); XMS_TRY(dalloc(s, q.d_nlen, n)); XMS_TRY(dalloc(s, q.d_lflag, n));
-        XMS_TRY(halloc(s, q.h_loff, n)); XMS_TRY(halloc(s, q.h_llen, n)); XMS_TRY(halloc(s, q.h_nlen, n)); XMS_TRY(halloc(s, q.h_lflag, n));
+        XMF_TRY(dalloc(s, q.d_lend, lines)); XMF_TRY(dalloc(s, q.d_lnext, lines));
+        XMF_TRY(dalloc(s, q.d_r_name_off, lines)); XMF_TRY(dalloc(s, q.d_r_name_len, lines)); XMF_TRY(dalloc(s, q.d_r_norm, lines));
+        XMF_TRY(dalloc(s, q.d_r_a, lines)); XMF_TRY(dalloc(s, q.d_r_x, lines)); XMF_TRY(dalloc(s, q.d_r_flag, lines + 64));
+        XMF_TRY(dalloc(s, q.d_blk_cnt, lines / SB + 2)); XMF_TRY(dalloc(s, q.d_blk_base, lines / SB + 2)); XMF_TRY(dalloc(s, q.d_sel, lines));
+        XMF_TRY(dalloc(s, q.d_loff, n)); XMF_TRY(dalloc(s, q.d_llen, n)); XMF_TRY(dalloc(s, q.d_nlen, n)); XMF_TRY(dalloc(s, q.d_lflag, n));
+        XMF_TRY(halloc(s, q.h_loff, n)); XMF_TRY(halloc(s, q.h_llen, n)); XMF_TRY(halloc(s, q.h_nlen, n)); XMF_TRY(halloc(s, q.h_lflag, n));
     }
-    for (int c = 0; c < 4; ++c) XMS_TRY(dalloc(s, sl.d_col[c], n));
-    XMS_TRY(dalloc(s, sl.d_bits, n / 64 + 2));
-    XMS_TRY(dalloc(s, sl.d_code, n));
-    XMS_TRY(dalloc(s, sl.d_bins4, (size_t)XM_BINS4_BYTES(records) + 16));
-    XMS_TRY(dalloc(s, sl.d_idx, n));
-    XMS_TRY(halloc(s, sl.h_code, n));
-    XMS_TRY(halloc(s, sl.h_idx, n));
+    XMF_TRY(sl.grow(s, records));
     sl.record_cap = records;
     return XM_OK;
 }
@@ -1023,10 +962,10 @@ int ensure_cigar(xm_strip *s, Slot &sl)
     const uint64_t ops_cap = std::min<uint64_t>(sl.window_cap / 2 + sl.record_cap + 16, 0xFFFFFFF0ull);
     for (int f = 0; f < 2; ++f) {
         PerFile &q = sl.pf[f];
-        XMS_TRY(dalloc(s, q.d_r_nm, lines)); XMS_TRY(dalloc(s, q.d_r_nops, lines)); XMS_TRY(dalloc(s, q.d_r_cig_off, lines));
-        XMS_TRY(dalloc(s, q.d_r_cig_len, lines));
-        XMS_TRY(dalloc(s, q.d_nm, n)); XMS_TRY(dalloc(s, q.d_cpos, n)); XMS_TRY(dalloc(s, q.d_cig_cnt, n));
-        XMS_TRY(dalloc(s, q.d_cig_tile, n / 256 + 4)); XMS_TRY(dalloc(s, q.d_cig_ops, (size_t)ops_cap + 16));
+        XMF_TRY(dalloc(s, q.d_r_nm, lines)); XMF_TRY(dalloc(s, q.d_r_nops, lines)); XMF_TRY(dalloc(s, q.d_r_cig_off, lines));
+        XMF_TRY(dalloc(s, q.d_r_cig_len, lines));
+        XMF_TRY(dalloc(s, q.d_nm, n)); XMF_TRY(dalloc(s, q.d_cpos, n)); XMF_TRY(dalloc(s, q.d_cig_cnt, n));
+        XMF_TRY(dalloc(s, q.d_cig_tile, n / 256 + 4)); XMF_TRY(dalloc(s, q.d_cig_ops, (size_t)ops_cap + 16));
         q.ops_cap = ops_cap;
     }
     sl.cigar_ready = true;
@@ -1041,7 +980,7 @@ int mark_chunks(xm_strip *s, Slot &sl, int file, uint64_t len, uint64_t usable, 
 {
     if (!last && upto_chunk > 0) --upto_chunk;
     if (upto_chunk <= sl.marked[file]) return XM_OK;
-    XMS_TRY(mark_range(s, sl, file, len, usable, sl.marked[file], upto_chunk));
+    XMF_TRY(mark_range(s, sl, file, len, usable, sl.marked[file], upto_chunk));
     sl.marked[file] = upto_chunk;
     return XM_OK;
 }
@@ -1050,7 +989,7 @@ int mark_range(xm_strip *s, Slot &sl, int file, uint64_t len, uint64_t usable, u
 {
     if (upto_chunk <= chunk0) return XM_OK;
     if (!sl.state_cleared) {
-        XMS_HIP(s, hipMemsetAsync(sl.d_state, 0, ST_WORDS * sizeof(uint32_t), sl.stream));
+        XMF_HIP(s, hipMemsetAsync(sl.d_state, 0, ST_WORDS * sizeof(uint32_t), sl.stream));
         sl.state_cleared = true;
     }
     PerFile &q = sl.pf[file];
@@ -1087,11 +1026,9 @@ int xm_strip_create(xm_ctx *ctx, int device_id, xm_strip **out)
         e = create_copy_stream(&sl.stream, before, k);
         for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&sl.ev[i]);
         if (e == hipSuccess) e = hipMalloc((void **)&sl.d_state, ST_WORDS * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_range, 4 * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc((void **)&sl.d_summary, SUM_WORDS * sizeof(uint64_t));
         if (e == hipSuccess) e = xmpin::host_malloc((void **)&sl.h_summary, SUM_WORDS * sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_off_counts, 72 * sizeof(uint64_t));
-        if (e == hipSuccess) e = xmpin::host_malloc((void **)&sl.h_off_counts, 74 * sizeof(uint64_t));
+        if (e == hipSuccess) e = sl.create();
         if (e == hipSuccess) e = hipMalloc((void **)&sl.d_gstate, 16 * sizeof(uint32_t));
         if (e == hipSuccess) e = xmpin::host_malloc((void **)&sl.h_gstate, 16 * sizeof(uint32_t));
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.ev_filled, hipEventDisableTiming);
@@ -1124,8 +1061,8 @@ int xm_strip_destroy(xm_strip *s)
         }
         if (sl.copy_stream) (void)hipStreamSynchronize(sl.copy_stream);
         free_slot(sl);
-        dfree(sl.d_state); dfree(sl.d_range); dfree(sl.d_summary); dfree(sl.d_off_counts);
-        hfree(sl.h_summary); hfree(sl.h_off_counts);
+        sl.destroy();
+        dfree(sl.d_state); dfree(sl.d_summary); hfree(sl.h_summary);
         dfree(sl.d_gstate); hfree(sl.h_gstate);
         if (sl.ev_filled) (void)hipEventDestroy(sl.ev_filled);
         if (sl.ev_out) (void)hipEventDestroy(sl.ev_out);
@@ -1143,10 +1080,10 @@ int xm_strip_reserve(xm_strip *s, int slot, uint64_t window_bytes, uint64_t max_
     if (!s || slot < 0 || slot >= XMS_SLOTS || window_bytes > XMS_MAX_WINDOW || max_records == 0 ||
         max_records >= 0xFFFFFF00ull)
         return XM_ERR_INVALID_ARG;
-    XMS_HIP(s, hipSetDevice(s->device));
+    XMF_HIP(s, hipSetDevice(s->device));
     Slot &sl = s->slot[slot];
-    XMS_HIP(s, hipStreamSynchronize(sl.stream));
-    if (sl.out_issued) XMS_HIP(s, hipEventSynchronize(sl.ev_out));            // THIS slot's last copy (the copy stream also carries the other slots')
+    XMF_HIP(s, hipStreamSynchronize(sl.stream));
+    if (sl.out_issued) XMF_HIP(s, hipEventSynchronize(sl.ev_out));            // THIS slot's last copy (the copy stream also carries the other slots')
     // a window begins here: whatever an abandoned one (a read that failed half way, a run that was never issued) had
     // sent is forgotten, or the next upload from offset 0 would be refused for ever
     sl.uploaded[0] = sl.uploaded[1] = 0;
@@ -1154,8 +1091,8 @@ int xm_strip_reserve(xm_strip *s, int slot, uint64_t window_bytes, uint64_t max_
     sl.state_cleared = false;
     sl.upload_timed = false;
     // a failed growth leaves the capacity at 0 and the pointers freed or null: the next reserve allocates afresh
-    XMS_TRY(grow_window(s, sl, std::max<uint64_t>(window_bytes, 1)));
-    XMS_TRY(grow_records(s, sl, max_records));
+    XMF_TRY(grow_window(s, sl, std::max<uint64_t>(window_bytes, 1)));
+    XMF_TRY(grow_records(s, sl, max_records));
     return XM_OK;
 }
 
@@ -1172,15 +1109,15 @@ int xm_strip_upload(xm_strip *s, int slot, int file, uint64_t offset, uint64_t b
     if (offset == 0) sl.uploaded[file] = 0;                 // a new window of this file (the previous one may have been abandoned)
     if (offset != sl.uploaded[file] || offset + bytes > sl.window_cap) return XM_ERR_INVALID_ARG;
     if (bytes == 0) return XM_OK;
-    XMS_HIP(s, hipSetDevice(s->device));
+    XMF_HIP(s, hipSetDevice(s->device));
     if (!sl.upload_timed) {
-        XMS_HIP(s, hipEventRecord(sl.ev[0], sl.stream));
+        XMF_HIP(s, hipEventRecord(sl.ev[0], sl.stream));
         sl.upload_timed = true;
     }
     if (offset == 0) sl.marked[file] = 0;
     // S1 on the chunks that are complete and not the last one staged so far (the window's last chunk needs its true length and
     // whether the window ends its file: xm_strip_run marks what is left)
-    XMS_TRY(mark_chunks(s, sl, file, offset + bytes, offset + bytes, (uint32_t)((offset + bytes) / CHUNK), false));
+    XMF_TRY(mark_chunks(s, sl, file, offset + bytes, offset + bytes, (uint32_t)((offset + bytes) / CHUNK), false));
     sl.uploaded[file] = offset + bytes;
     return XM_OK;
 }
@@ -1199,9 +1136,9 @@ int xm_strip_run(xm_strip *s, int slot, uint64_t len1, int eof1, uint64_t len2, 
     sl.classified = false;
     if (len1 > sl.window_cap || len2 > sl.window_cap || max_records == 0 || max_records > sl.record_cap || sent[0] > len1 || sent[1] > len2)
         return XM_ERR_INVALID_ARG;
-    XMS_HIP(s, hipSetDevice(s->device));
+    XMF_HIP(s, hipSetDevice(s->device));
     const bool cigar = score_mode == XMS_SCORE_CIGAR;
-    if (cigar) XMS_TRY(ensure_cigar(s, sl));
+    if (cigar) XMF_TRY(ensure_cigar(s, sl));
     const uint64_t len[2] = {len1, len2};
     const int eof[2] = {eof1, eof2};
     Job job;
@@ -1240,7 +1177,7 @@ int xm_strip_run(xm_strip *s, int slot, uint64_t len1, int eof1, uint64_t len2, 
     job.unit_bits = sl.d_bits;
 
     hipStream_t st = sl.stream;
-    if (!timed) XMS_HIP(s, hipEventRecord(sl.ev[0], st));
+    if (!timed) XMF_HIP(s, hipEventRecord(sl.ev[0], st));
     for (int f = 0; f < 2; ++f)
         if (sent[f] == 0) sl.marked[f] = 0;            // nothing of this window was announced: all of it is marked here
     // S1 on what is left of each window (that is where the text crosses the link; the last chunk always is left)
@@ -1248,10 +1185,10 @@ int xm_strip_run(xm_strip *s, int slot, uint64_t len1, int eof1, uint64_t len2, 
         const int rc = mark_chunks(s, sl, f, len[f], job.f[f].usable, job.f[f].n_chunks, true);
         if (rc != XM_OK) { sl.state_cleared = false; sl.marked[0] = sl.marked[1] = 0; return rc; }
     }
-    if (!sl.state_cleared) XMS_HIP(s, hipMemsetAsync(sl.d_state, 0, ST_WORDS * sizeof(uint32_t), st));   // two empty windows
+    if (!sl.state_cleared) XMF_HIP(s, hipMemsetAsync(sl.d_state, 0, ST_WORDS * sizeof(uint32_t), st));   // two empty windows
     sl.state_cleared = false;
     sl.marked[0] = sl.marked[1] = 0;
-    XMS_HIP(s, hipEventRecord(sl.ev[1], st));
+    XMF_HIP(s, hipEventRecord(sl.ev[1], st));
     chunk_scan_kernel<<<2, 1024, 0, st>>>(job);
     fill_kernel<<<dim3(max_chunks, 2), SB, 0, st>>>(job);
     // a line takes at least one byte of its window: no more lines than that, no more records than both files have lines
@@ -1274,10 +1211,10 @@ int xm_strip_run(xm_strip *s, int slot, uint64_t len1, int eof1, uint64_t len2, 
         cig_write_kernel<<<dim3(rec_blocks, 2), SB, 0, st>>>(job);
     }
     summary_kernel<<<1, 64, 0, st>>>(job);
-    XMS_HIP(s, hipGetLastError());
-    XMS_HIP(s, hipEventRecord(sl.ev[2], st));
-    XMS_HIP(s, hipMemcpyAsync(sl.h_summary, sl.d_summary, SUM_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    XMS_HIP(s, hipStreamSynchronize(st));
+    XMF_HIP(s, hipGetLastError());
+    XMF_HIP(s, hipEventRecord(sl.ev[2], st));
+    XMF_HIP(s, hipMemcpyAsync(sl.h_summary, sl.d_summary, SUM_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    XMF_HIP(s, hipStreamSynchronize(st));
 
     const uint64_t *sum = sl.h_summary;
     const uint64_t n = sum[SUM_N];
@@ -1297,12 +1234,12 @@ int xm_strip_run(xm_strip *s, int slot, uint64_t len1, int eof1, uint64_t len2, 
     if (n) {
         for (int f = 0; f < 2; ++f) {
             PerFile &q = sl.pf[f];
-            XMS_HIP(s, hipMemcpyAsync(q.h_loff, q.d_loff, n * 4, hipMemcpyDeviceToHost, st));
-            XMS_HIP(s, hipMemcpyAsync(q.h_llen, q.d_llen, n * 4, hipMemcpyDeviceToHost, st));
-            XMS_HIP(s, hipMemcpyAsync(q.h_nlen, q.d_nlen, n * 4, hipMemcpyDeviceToHost, st));
-            XMS_HIP(s, hipMemcpyAsync(q.h_lflag, q.d_lflag, n, hipMemcpyDeviceToHost, st));
+            XMF_HIP(s, hipMemcpyAsync(q.h_loff, q.d_loff, n * 4, hipMemcpyDeviceToHost, st));
+            XMF_HIP(s, hipMemcpyAsync(q.h_llen, q.d_llen, n * 4, hipMemcpyDeviceToHost, st));
+            XMF_HIP(s, hipMemcpyAsync(q.h_nlen, q.d_nlen, n * 4, hipMemcpyDeviceToHost, st));
+            XMF_HIP(s, hipMemcpyAsync(q.h_lflag, q.d_lflag, n, hipMemcpyDeviceToHost, st));
         }
-        XMS_HIP(s, hipStreamSynchronize(st));
+        XMF_HIP(s, hipStreamSynchronize(st));
     }
     uint64_t n_exc = 0;
     for (int f = 0; f < 2; ++f)
@@ -1328,41 +1265,12 @@ int xm_strip_classify(xm_strip *s, int slot, int mode, uint64_t n_records, int32
     *idx = sl.h_idx;
     std::memset(bin_offsets, 0, 8 * sizeof(uint64_t));
     std::memset(counts, 0, 64 * sizeof(uint64_t));
-    if (n_records == 0) return XM_OK;
-    XMS_HIP(s, hipSetDevice(s->device));
-    hipStream_t st = sl.stream;
-    const bool cigar = sl.last_score_mode == XMS_SCORE_CIGAR;
-    int rc;
-    if (cigar) {
-        XMS_HIP(s, hipMemsetAsync(sl.d_range, 0, sizeof(uint32_t), st));
-        const PerFile &a = sl.pf[0], &b = sl.pf[1];
-        rc = xm_classify_compact_cigar_packed_dev(s->ctx, st, mode, n_records, a.d_nm, a.d_cig_cnt, a.d_cig_tile, a.d_cig_ops, sl.d_col[1],
-                                                  b.d_nm, b.d_cig_cnt, b.d_cig_tile, b.d_cig_ops, sl.d_col[3], sl.d_bits, min_score_floor,
-                                                  sl.d_code, sl.d_bins4, sl.d_range, sl.d_idx, sl.d_off_counts, sl.d_off_counts + 8);
-    } else {
-        rc = xm_classify_compact_dev(s->ctx, st, mode, n_records, sl.d_col[0], sl.d_col[1], sl.d_col[2], sl.d_col[3], sl.d_bits,
-                                     min_score_floor, sl.d_code, sl.d_bins4, sl.d_idx, sl.d_off_counts, sl.d_off_counts + 8);
-    }
-    if (rc != XM_OK) {
-        std::lock_guard<std::mutex> hold(s->error_lock);
-        s->last_error = xm_last_hip_error(s->ctx);
-        return rc;
-    }
-    XMS_HIP(s, hipMemcpyAsync(sl.h_code, sl.d_code, n_records, hipMemcpyDeviceToHost, st));
-    XMS_HIP(s, hipMemcpyAsync(sl.h_off_counts, sl.d_off_counts, 72 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (cigar) XMS_HIP(s, hipMemcpyAsync(sl.h_off_counts + 72, sl.d_range, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    XMS_HIP(s, hipStreamSynchronize(st));
-    if (cigar && *reinterpret_cast<const uint32_t *>(sl.h_off_counts + 72) != 0u) return XM_ERR_RANGE;
-    const uint64_t units = sl.h_off_counts[7];
-    if (units > n_records) return XM_ERR_HIP;
-    if (units) {
-        XMS_HIP(s, hipMemcpyAsync(sl.h_idx, sl.d_idx, units * 4, hipMemcpyDeviceToHost, st));
-        XMS_HIP(s, hipStreamSynchronize(st));
-    }
-    std::memcpy(bin_offsets, sl.h_off_counts, 8 * sizeof(uint64_t));
-    std::memcpy(counts, sl.h_off_counts + 8, 64 * sizeof(uint64_t));
-    sl.classified = true;
-    return XM_OK;
+    if (n_records == 0) return XM_OK;                  // (`classified` stays unset: xm_strip_fetch_bins then refuses the slot)
+    XMF_HIP(s, hipSetDevice(s->device));
+    const PerFile &a = sl.pf[0], &b = sl.pf[1];
+    const CigCols cig[2] = {{a.d_nm, a.d_cig_cnt, a.d_cig_tile, a.d_cig_ops}, {b.d_nm, b.d_cig_cnt, b.d_cig_tile, b.d_cig_ops}};
+    return sl.run_fused(s, sl.stream, mode, n_records, min_score_floor, sl.last_score_mode == XMS_SCORE_CIGAR ? cig : nullptr,
+                        bin_offsets, counts);
 }
 
 int xm_strip_fetch_bins(xm_strip *s, int slot, uint64_t n_records, int paired, uint32_t sink_mask, xm_strip_bins *out)
@@ -1372,59 +1280,41 @@ int xm_strip_fetch_bins(xm_strip *s, int slot, uint64_t n_records, int paired, u
     if (n_records > sl.record_cap || n_records > 0xFFFFFFF0ull || sl.last_score_mode < 0 || !sl.classified) return XM_ERR_INVALID_ARG;
     std::memset(out, 0, sizeof *out);
     const uint32_t n = (uint32_t)n_records;
-    const uint64_t units64 = sl.h_off_counts[7];                                    // of the slot's last xm_strip_classify
+    const uint64_t units64 = sl.h_off_counts[7];                                           // of the slot's last xm_strip_classify
     if (n == 0 || units64 == 0) return XM_OK;
     if (units64 > n_records) return XM_ERR_INVALID_ARG;
     const uint32_t n_units = (uint32_t)units64;
-    XMS_HIP(s, hipSetDevice(s->device));
+    XMF_HIP(s, hipSetDevice(s->device));
     // the stream of the six outputs: both windows' text at most (+ a '\n' per line that had none), unless units overlap
     const uint64_t want_cap = std::min<uint64_t>(2 * sl.window_cap + 4096, 0xFFFFFFF0ull);
     if (sl.out_cap < want_cap) {
-        XMS_HIP(s, hipStreamSynchronize(sl.copy_stream));
+        XMF_HIP(s, hipStreamSynchronize(sl.copy_stream));
         sl.out_cap = 0;
-        XMS_TRY(dalloc(s, sl.d_out, (size_t)want_cap + 64)); XMS_TRY(halloc(s, sl.h_out, (size_t)want_cap + 64));
+        XMF_TRY(dalloc(s, sl.d_out, (size_t)want_cap + 64)); XMF_TRY(halloc(s, sl.h_out, (size_t)want_cap + 64));
         sl.out_cap = want_cap;
     }
-    if (sl.out_records < sl.record_cap) {
-        sl.out_records = 0;
-        const size_t nr = (size_t)sl.record_cap + 64;
-        XMS_TRY(dalloc(s, sl.d_usize, nr)); XMS_TRY(dalloc(s, sl.d_uplace, nr)); XMS_TRY(dalloc(s, sl.d_upart, nr / SCAN_TILE + 8));
-        sl.out_records = sl.record_cap;
-    }
+    XMF_TRY(sl.reserve_units(s, sl.record_cap));
     out->text = sl.h_out;
     hipStream_t st = sl.stream;
-    if (sl.out_issued) XMS_HIP(s, hipStreamWaitEvent(st, sl.ev_out, 0));            // the previous window's stream has left d_out
-    const uint32_t n_part = (n_units + SCAN_TILE - 1u) / SCAN_TILE;
+    if (sl.out_issued) XMF_HIP(s, hipStreamWaitEvent(st, sl.ev_out, 0));            // the previous window's stream has left d_out
     const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(sl.d_off_counts);
     const PerFile &a = sl.pf[0], &b = sl.pf[1];
-    XMS_HIP(s, hipMemsetAsync(sl.d_gstate, 0, 16 * sizeof(uint32_t), st));
-    // gstate: [0] a wanted line that is not '\t'.join(fields) as it stands, [1] the scan's 32-bit total, [2..3] the 64-bit total,
-    // [4..11] where each bin's text begins
+    XMF_HIP(s, hipMemsetAsync(sl.d_gstate + GS_FLAG, 0, GS_LIVE_BYTES, st));
     sam_unit_size_kernel<<<(n_units + 255u) / 256u, 256, 0, st>>>(sl.d_idx, d_off, n_units, n, paired ? 1 : 0, sink_mask, a.d_llen, b.d_llen,
                                                                  a.d_lflag, b.d_lflag, sl.d_usize,
-                                                                 reinterpret_cast<unsigned long long *>(sl.d_gstate + 2), sl.d_gstate + 0);
-    size_sum_kernel<<<n_part, 256, 0, st>>>(sl.d_usize, n_units, sl.d_upart);
-    part_scan_kernel<<<1, 1024, 0, st>>>(sl.d_upart, n_part, sl.d_gstate + 1);
-    size_place_kernel<true><<<n_part, 256, 0, st>>>(sl.d_usize, n_units, sl.d_upart, sl.d_uplace);
-    bin_start_kernel<<<1, 64, 0, st>>>(sl.d_uplace, d_off, n_units, sl.d_gstate + 1, sl.d_gstate + 4);
-    XMS_HIP(s, hipMemcpyAsync(sl.h_gstate, sl.d_gstate, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    XMS_HIP(s, hipStreamSynchronize(st));
-    XMS_HIP(s, hipGetLastError());
-    if (sl.h_gstate[0] != 0u) { out->status = 3; return XM_OK; }            // a line the writer has to re-join: the host's window
-    uint64_t total = 0;
-    std::memcpy(&total, sl.h_gstate + 2, sizeof total);
-    if (total > sl.out_cap) { out->status = 2; return XM_OK; }              // more text than the buffers hold (overlapping units)
-    for (int k = 0; k < 8; ++k) out->bin_off[k] = sl.h_gstate[4 + k];
+                                                                 reinterpret_cast<unsigned long long *>(sl.d_gstate + GS_TOTAL64),
+                                                                 sl.d_gstate + GS_FLAG);
+    Placed at;
+    XMF_TRY(sl.place_units(s, st, n_units, d_off, sl.d_gstate, sl.h_gstate, nullptr, at));
+    if (at.flag != 0u) { out->status = 3; return XM_OK; }                   // a line the writer has to re-join: the host's window
+    if (at.total > sl.out_cap) { out->status = 2; return XM_OK; }           // more text than the buffers hold (overlapping units)
+    for (int k = 0; k < 8; ++k) out->bin_off[k] = at.starts[k];
     sam_line_copy_kernel<<<((paired ? 2u : 1u) * n_units + 3u) / 4u, 256, 0, st>>>(
         a.d_text, b.d_text, a.d_loff, b.d_loff, a.d_llen, b.d_llen, sl.d_idx, d_off, n_units, n, paired ? 1 : 0, sink_mask, sl.d_usize, sl.d_uplace,
         sl.d_out, (uint32_t)sl.out_cap);
-    XMS_HIP(s, hipEventRecord(sl.ev_filled, st));
-    XMS_HIP(s, hipStreamWaitEvent(sl.copy_stream, sl.ev_filled, 0));
-    out_copy(sl.d_out, sl.h_out, total, sl.copy_stream);
-    XMS_HIP(s, hipEventRecord(sl.ev_out, sl.copy_stream));
+    const int rc = Slot::send_home(s, st, sl.copy_stream, sl.ev_filled, sl.ev_out, sl.d_out, sl.h_out, at.total);
     sl.out_issued = true;
-    XMS_HIP(s, hipGetLastError());
-    return XM_OK;
+    return rc;
 }
 
 int xm_strip_out_wait(xm_strip *s, int slot)
@@ -1432,8 +1322,8 @@ int xm_strip_out_wait(xm_strip *s, int slot)
     if (!s || slot < 0 || slot >= XMS_SLOTS) return XM_ERR_INVALID_ARG;
     Slot &sl = s->slot[slot];
     if (!sl.out_issued) return XM_OK;
-    XMS_HIP(s, hipSetDevice(s->device));
-    XMS_HIP(s, hipEventSynchronize(sl.ev_out));
+    XMF_HIP(s, hipSetDevice(s->device));
+    XMF_HIP(s, hipEventSynchronize(sl.ev_out));
     return XM_OK;
 }
 
@@ -1444,14 +1334,8 @@ int xm_strip_columns(xm_strip *s, int slot, uint64_t n_records, int32_t *as1, in
     Slot &sl = s->slot[slot];
     if (n_records > sl.record_cap) return XM_ERR_INVALID_ARG;
     if (n_records == 0) return XM_OK;
-    XMS_HIP(s, hipSetDevice(s->device));
-    int32_t *dst[4] = {as1, xs1, as2, xs2};
-    for (int c = 0; c < 4; ++c)
-        if (dst[c]) XMS_HIP(s, hipMemcpyAsync(dst[c], sl.d_col[c], n_records * 4, hipMemcpyDeviceToHost, sl.stream));
-    if (unit_bits)
-        XMS_HIP(s, hipMemcpyAsync(unit_bits, sl.d_bits, (n_records + 63) / 64 * 8, hipMemcpyDeviceToHost, sl.stream));
-    XMS_HIP(s, hipStreamSynchronize(sl.stream));
-    return XM_OK;
+    XMF_HIP(s, hipSetDevice(s->device));
+    return sl.columns_to_host(s, sl.stream, n_records, as1, xs1, as2, xs2, unit_bits);
 }
 
 int xm_strip_cigar_columns(xm_strip *s, int slot, int file, uint64_t n_records, int32_t *nm, uint8_t *cig_cnt, uint32_t *cig_tile,
@@ -1462,18 +1346,18 @@ int xm_strip_cigar_columns(xm_strip *s, int slot, int file, uint64_t n_records, 
     if (n_records > sl.record_cap || sl.last_score_mode != XMS_SCORE_CIGAR) return XM_ERR_INVALID_ARG;
     *n_ops = 0;
     if (n_records == 0) return XM_OK;
-    XMS_HIP(s, hipSetDevice(s->device));
+    XMF_HIP(s, hipSetDevice(s->device));
     const PerFile &q = sl.pf[file];
     const size_t tiles = (size_t)XM_CIG_TILES(n_records) + 1;
     uint32_t last = 0;
-    XMS_HIP(s, hipMemcpy(&last, q.d_cig_tile + tiles - 1, 4, hipMemcpyDeviceToHost));
+    XMF_HIP(s, hipMemcpy(&last, q.d_cig_tile + tiles - 1, 4, hipMemcpyDeviceToHost));
     *n_ops = last;
-    if (nm) XMS_HIP(s, hipMemcpy(nm, q.d_nm, n_records * 4, hipMemcpyDeviceToHost));
-    if (cig_cnt) XMS_HIP(s, hipMemcpy(cig_cnt, q.d_cig_cnt, n_records, hipMemcpyDeviceToHost));
-    if (cig_tile) XMS_HIP(s, hipMemcpy(cig_tile, q.d_cig_tile, tiles * 4, hipMemcpyDeviceToHost));
+    if (nm) XMF_HIP(s, hipMemcpy(nm, q.d_nm, n_records * 4, hipMemcpyDeviceToHost));
+    if (cig_cnt) XMF_HIP(s, hipMemcpy(cig_cnt, q.d_cig_cnt, n_records, hipMemcpyDeviceToHost));
+    if (cig_tile) XMF_HIP(s, hipMemcpy(cig_tile, q.d_cig_tile, tiles * 4, hipMemcpyDeviceToHost));
     if (cig_ops) {
         if (ops_capacity < last) return XM_ERR_INVALID_ARG;
-        if (last) XMS_HIP(s, hipMemcpy(cig_ops, q.d_cig_ops, (size_t)last * 4, hipMemcpyDeviceToHost));
+        if (last) XMF_HIP(s, hipMemcpy(cig_ops, q.d_cig_ops, (size_t)last * 4, hipMemcpyDeviceToHost));
     }
     return XM_OK;
 }
@@ -1487,16 +1371,6 @@ int xm_strip_device_columns(xm_strip *s, int slot, void *ptrs[5])
     return XM_OK;
 }
 
-const char *xm_strip_last_error(const xm_strip *s)
-{
-    // the other slot's thread may be assigning the text: copied under the lock into a buffer of the calling thread
-    static thread_local std::string mine;
-    if (!s) return "";
-    {
-        std::lock_guard<std::mutex> hold(const_cast<xm_strip *>(s)->error_lock);
-        mine = s->last_error;
-    }
-    return mine.c_str();
-}
+const char *xm_strip_last_error(const xm_strip *s) { return last_error_text(s); }
 
 }  // extern "C"
