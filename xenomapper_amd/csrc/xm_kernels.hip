@@ -87,6 +87,7 @@ __device__ __forceinline__ uint32_t bin_of_code(int mode, uint32_t c)
 template <typename T> struct Vec4;
 typedef int32_t v4i32 __attribute__((ext_vector_type(4)));
 typedef int32_t v4i32_a4 __attribute__((ext_vector_type(4), aligned(4)));   // dword-aligned 16-byte access
+typedef uint32_t v8u32_a4 __attribute__((ext_vector_type(8), aligned(4)));  // dword-aligned 32-byte access
 typedef double  v4f64 __attribute__((ext_vector_type(4)));
 template <> struct Vec4<int32_t> { typedef v4i32 type; };
 template <> struct Vec4<double>  { typedef v4f64 type; };
@@ -314,6 +315,63 @@ __device__ __forceinline__ void classify_finish(const T a1[4], const T x1[4], co
 // NT: the score columns are read once and never again, so they are loaded non-temporally; the
 // category bytes are stored with the default policy because K2 reads them next (100 MB at the
 // 50 M-pair configuration, which fits the 256 MiB Infinity Cache).
+// The loads of a lane's group of 4 records (group g = wg * BLOCK + threadIdx.x of the whole input): the four score
+// columns, the unit flags `mb`, and `halo` = the state of the record in front of the workgroup's range.
+template <typename T, bool PAIRED, bool NT, int BLOCK, bool FULL>
+__device__ __forceinline__ void classify_load(const T *__restrict__ as1, const T *__restrict__ xs1,
+                                              const T *__restrict__ as2, const T *__restrict__ xs2,
+                                              const uint8_t *__restrict__ unit_bits8, T m, uint64_t n, uint64_t wg,
+                                              T a1[4], T x1[4], T a2[4], T x2[4], uint32_t &mb, uint32_t &halo)
+{
+    const uint64_t g = wg * BLOCK + threadIdx.x;
+    const uint64_t r0 = g * 4;
+    mb = 0;
+    halo = 0;
+    if (FULL) {
+        // The unit flags of a wave's 256 records are 32 consecutive bytes at a wave-uniform address: eight scalar dwords
+        // (no vector-memory instruction), each lane picks its nibble out of them.
+        const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        const uint32_t lane = threadIdx.x & 63u;
+        const v8u32_a4 mw = *reinterpret_cast<const v8u32_a4 *>(unit_bits8 + wg * (BLOCK / 2) + wave * 32u);
+        load4<T, NT, true>(as1, r0, n, a1);
+        load4<T, NT, true>(xs1, r0, n, x1);
+        load4<T, NT, true>(as2, r0, n, a2);
+        load4<T, NT, true>(xs2, r0, n, x2);
+        uint32_t d = mw[0];
+#pragma unroll
+        for (uint32_t k = 1; k < 8u; ++k) d = ((lane >> 3) == k) ? mw[k] : d;
+        mb = (d >> ((lane & 7u) * 4u)) & 0xFu;
+        // The record in front of the workgroup's range is fetched only where the workgroup's first record closes a unit
+        // (never with strictly interleaved mates: workgroups begin at even records).  The test is the first wave's first
+        // flag, a scalar one, made while the column loads above are in flight; the fetch, at a uniform address, is scalar
+        // too.  (Fetched by every workgroup it cost K1 12 us of 286 per 100 M records, profiles/r07_k1_ablation.txt.)
+        if (PAIRED && wave == 0u) {
+            if (wg == 0) {
+                if (lane == 0u) mb &= ~1u;                     // record 0 has no predecessor (:402)
+            } else if (mw[0] & 1u) {
+                const uint64_t h = wg * (BLOCK * 4) - 1;
+                halo = mapping_state<T>(as1[h], xs1[h], as2[h], xs2[h], m);
+            }
+        }
+    } else {
+        // the last, partial workgroup: a byte load per lane, bounds tests
+        if (r0 < n) mb = (uint32_t)(unit_bits8[g >> 1] >> ((g & 1u) * 4u)) & 0xFu;
+        load4<T, NT, false>(as1, r0, n, a1);
+        load4<T, NT, false>(xs1, r0, n, x1);
+        load4<T, NT, false>(as2, r0, n, a2);
+        load4<T, NT, false>(xs2, r0, n, x2);
+        if (r0 + 4 > n) mb &= (r0 < n) ? ((1u << (uint32_t)(n - r0)) - 1u) : 0u;
+        if (PAIRED && threadIdx.x == 0) {
+            if (r0 == 0) {
+                mb &= ~1u;                                     // record 0 has no predecessor (:402)
+            } else if (mb & 1u) {
+                const uint64_t h = r0 - 1;                     // thread 0's r0 < n (grid sizing), so h < n
+                halo = mapping_state<T>(as1[h], xs1[h], as2[h], xs2[h], m);
+            }
+        }
+    }
+}
+
 template <typename T, bool PAIRED, bool NT, int BLOCK, bool FULL, bool COUNTS, int BINMODE>
 __device__ __forceinline__ void classify_body(const T *__restrict__ as1, const T *__restrict__ xs1,
                                               const T *__restrict__ as2, const T *__restrict__ xs2,
@@ -321,28 +379,11 @@ __device__ __forceinline__ void classify_body(const T *__restrict__ as1, const T
                                               uint8_t *__restrict__ code, uint64_t n, uint32_t *last_state,
                                               uint32_t *count_lds, const CountSink &sink)
 {
-    const uint64_t g = (uint64_t)(blockIdx.x + sink.blk0) * BLOCK + threadIdx.x;       // group of 4 records
-    const uint64_t r0 = g * 4;
-
+    const uint64_t wg = (uint64_t)blockIdx.x + sink.blk0;                              // workgroup of the whole input
+    const uint64_t r0 = (wg * BLOCK + threadIdx.x) * 4;
     T a1[4], x1[4], a2[4], x2[4];
-    load4<T, NT, FULL>(as1, r0, n, a1);
-    load4<T, NT, FULL>(xs1, r0, n, x1);
-    load4<T, NT, FULL>(as2, r0, n, a2);
-    load4<T, NT, FULL>(xs2, r0, n, x2);
-    uint32_t mb = 0;
-    if (FULL || r0 < n) mb = (uint32_t)(unit_bits8[g >> 1] >> ((g & 1u) * 4u)) & 0xFu;
-    if (!FULL && r0 + 4 > n) mb &= (r0 < n) ? ((1u << (uint32_t)(n - r0)) - 1u) : 0u;
-
-    // the record in front of the workgroup's range (thread 0 only)
-    uint32_t halo = 0;
-    if (PAIRED && threadIdx.x == 0) {
-        if (r0 > 0) {
-            const uint64_t h = r0 - 1;                         // thread 0's r0 < n (grid sizing), so h < n
-            halo = mapping_state<T>(as1[h], xs1[h], as2[h], xs2[h], m);
-        } else {
-            mb &= ~1u;                                         // record 0 has no predecessor (:402)
-        }
-    }
+    uint32_t mb, halo;
+    classify_load<T, PAIRED, NT, BLOCK, FULL>(as1, xs1, as2, xs2, unit_bits8, m, n, wg, a1, x1, a2, x2, mb, halo);
     classify_finish<T, PAIRED, BLOCK, FULL, COUNTS, BINMODE>(a1, x1, a2, x2, m, mb, halo, last_state, code, r0, n, count_lds, sink);
 }
 
@@ -955,25 +996,9 @@ __device__ __forceinline__ void classify_runs_body(const T *__restrict__ as1, co
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t g = blockIdx.x;
-    const uint64_t g4 = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    const uint64_t r0 = g4 * 4;
     T a1[4], x1[4], a2[4], x2[4];
-    load4<T, NT, FULL>(as1, r0, n, a1);
-    load4<T, NT, FULL>(xs1, r0, n, x1);
-    load4<T, NT, FULL>(as2, r0, n, a2);
-    load4<T, NT, FULL>(xs2, r0, n, x2);
-    uint32_t mb = 0;
-    if (FULL || r0 < n) mb = (uint32_t)(unit_bits8[g4 >> 1] >> ((g4 & 1u) * 4u)) & 0xFu;
-    if (!FULL && r0 + 4 > n) mb &= (r0 < n) ? ((1u << (uint32_t)(n - r0)) - 1u) : 0u;
-    uint32_t halo = 0;
-    if (PAIRED && threadIdx.x == 0) {
-        if (r0 > 0) {
-            const uint64_t h = r0 - 1;
-            halo = mapping_state<T>(as1[h], xs1[h], as2[h], xs2[h], m);
-        } else {
-            mb &= ~1u;                                                    // record 0 has no predecessor (:402)
-        }
-    }
+    uint32_t mb, halo;
+    classify_load<T, PAIRED, NT, BLOCK, FULL>(as1, xs1, as2, xs2, unit_bits8, m, n, g, a1, x1, a2, x2, mb, halo);
     uint32_t s[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) s[j] = mapping_state<T>(a1[j], x1[j], a2[j], x2[j], m);
