@@ -25,8 +25,9 @@
 extern "C" {
 #endif
 
-#define XMB_ABI_VERSION 4   /* 2: xm_bamdev_fetch_bins; f and B:f fields printed on the device.  3: raw1 / raw2 exist from the
-                               first xm_bamdev_fetch_raw on (xm_bamdev_raw).  4: xm_bamdev_fetch_bins_bam */
+#define XMB_ABI_VERSION 5   /* 2: xm_bamdev_fetch_bins; f and B:f fields printed on the device.  3: raw1 / raw2 exist from the
+                               first xm_bamdev_fetch_raw on (xm_bamdev_raw).  4: xm_bamdev_fetch_bins_bam.  5: xm_bgzf_deflate_dev,
+                               xm_bgzf_compress */
 
 /* One BGZF block of the compressed image (24 bytes; the layout the kernels read). */
 typedef struct {
@@ -98,6 +99,41 @@ int xm_bgzf_inflate_walk_dev(xm_ctx *ctx, void *stream, const uint8_t *comp, con
  * crc_out[b] for b < n_blocks, on the device.  One wave per block. */
 int xm_bgzf_crc32_dev(xm_ctx *ctx, void *stream, const uint8_t *out, const xm_bgzf_block *blocks, uint64_t n_blocks,
                       uint32_t *crc_out);
+
+/*
+ * The way back (XMB_ABI_VERSION 5): n_blocks payloads deflated on the GPU, one raw-DEFLATE stream each (RFC 1951: one dynamic-Huffman
+ * block, or one stored block where that is not shorter; BFINAL set) -- what stands between a BGZF member's header and its trailer.
+ * blocks: the descriptors the two calls above take, on the device, read only.  Block b's payload is the isize bytes at in + out_off
+ * (any alignment; isize <= XMB_DEFLATE_MAX_ISIZE); its stream goes to comp + cdata_off (comp and cdata_off 16-byte aligned), where
+ * cdata_len bytes are free -- the CAPACITY of that place, at least XMB_DEFLATE_BOUND(isize); clen[b] receives the stream's length.
+ * The same descriptors with cdata_len = clen[b] are what xm_bgzf_inflate_dev takes.  status[b]: 0, or XMB_DEFLATE_ERR_* -- then
+ * clen[b] = 0 and nothing of that block is written.
+ * in: readable up to 15 bytes behind every payload (the match search loads 16 bytes at a time; what it reads there does not
+ * matter).  Nothing is written outside a block's own [cdata_off, cdata_off + XMB_DEFLATE_BOUND(isize)) and `work`.
+ * work: device scratch, 16-byte aligned -- the launch's block counter (zeroed by the call) and 255 KB per chain of lanes;
+ * the value of the work_bytes call lets the launch run as many chains as it ever does (<= 256 MiB), less is accepted down to
+ * one chain's (261 376 bytes) and only makes the launch narrower.  The streams do not depend on it, nor on anything but the payload's
+ * bytes.  n_blocks == 0: XM_OK without a launch.  Only enqueues work.
+ */
+#define XMB_DEFLATE_MAX_ISIZE 65280u
+#define XMB_DEFLATE_BOUND(isize) ((isize) + 5u)              /* bytes a block's stream never exceeds */
+#define XMB_DEFLATE_ERR_ISIZE 32u                            /* isize > XMB_DEFLATE_MAX_ISIZE */
+#define XMB_DEFLATE_ERR_CAPACITY 33u                         /* cdata_len < XMB_DEFLATE_BOUND(isize) */
+#define XMB_DEFLATE_ERR_ALIGN 34u                            /* cdata_off not a multiple of 16 */
+uint64_t xm_bgzf_deflate_work_bytes(void);
+int xm_bgzf_deflate_dev(xm_ctx *ctx, void *stream, const uint8_t *in, const xm_bgzf_block *blocks, uint64_t n_blocks,
+                        uint8_t *comp, uint32_t *clen, uint32_t *status, void *work, uint64_t work_bytes);
+
+/*
+ * Host buffers in, BGZF out, blocking: data[0 .. len) is cut every block_payload bytes (64 .. 65280; 0 = 65280), the pieces are
+ * deflated (the call above), CRC'd (xm_bgzf_crc32_dev) and packed into complete BGZF members on the device; out receives them
+ * back to back, *out_len their bytes.  No member for len == 0, and no end-of-file member: the caller appends the 28 bytes.
+ * XM_ERR_INVALID_ARG when out_cap < XMB_COMPRESS_BOUND(len, payload in use).  Inputs beyond 64 MiB go through the device in
+ * windows; the call frees what it allocated and leaves nothing page-locked.
+ */
+#define XMB_COMPRESS_BOUND(len, payload) ((len) + 31u * (((len) + (payload) - 1u) / (payload)))
+int xm_bgzf_compress(xm_ctx *ctx, const uint8_t *data, uint64_t len, uint32_t block_payload,
+                     uint8_t *out, uint64_t out_cap, uint64_t *out_len);
 
 const char *xm_bgzf_strerror(uint32_t block_status);
 

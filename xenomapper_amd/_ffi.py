@@ -158,6 +158,9 @@ def lib():
         "xm_bgzf_inflate_walk_dev": ([P, P, P, P, U64, P, P, P, P], I),
         "xm_bgzf_crc32_dev": ([P, P, P, P, U64, P], I),
         "xm_bgzf_strerror": ([ctypes.c_uint32], ctypes.c_char_p),
+        "xm_bgzf_deflate_work_bytes": ([], U64),
+        "xm_bgzf_deflate_dev": ([P, P, P, P, U64, P, P, P, P, U64], I),
+        "xm_bgzf_compress": ([P, P, U64, ctypes.c_uint32, P, U64, ctypes.POINTER(U64)], I),
         "xm_bamdev_create": ([P, I, ctypes.POINTER(P)], I),
         "xm_bamdev_destroy": ([P], I),
         "xm_bamdev_reserve": ([P, I, U64, U64, U64, U64], I),
@@ -198,6 +201,7 @@ EXPORTED = ("xm_abi_version", "xm_strerror", "xm_last_hip_error", "xm_ctx_create
             "xms_abi_version", "xm_strip_create", "xm_strip_destroy", "xm_strip_reserve", "xm_strip_staging", "xm_strip_upload", "xm_strip_run",
             "xm_strip_classify", "xm_strip_fetch_bins", "xm_strip_out_wait", "xm_strip_columns", "xm_strip_cigar_columns", "xm_strip_device_columns", "xm_strip_last_error",
             "xm_bgzf_index", "xm_bgzf_index_prefix", "xm_bgzf_inflate_dev", "xm_bgzf_inflate_walk_dev", "xm_bgzf_crc32_dev", "xm_bgzf_strerror",
+            "xm_bgzf_deflate_work_bytes", "xm_bgzf_deflate_dev", "xm_bgzf_compress",
             "xm_bamdev_create", "xm_bamdev_destroy", "xm_bamdev_reserve", "xm_bamdev_staging", "xm_bamdev_run", "xm_bamdev_raw_wait", "xm_bamdev_fetch_raw", "xm_bamdev_raw", "xm_bamdev_fetch_wanted", "xm_bamdev_fetch_text", "xm_bamdev_fetch_bins", "xm_bamdev_fetch_bins_bam", "xm_bamdev_set_refs", "xm_bamdev_upload", "xm_bamdev_classify",
             "xm_bamdev_columns", "xm_bamdev_cigar_columns", "xm_bamdev_last_error")
 
@@ -700,6 +704,33 @@ class Context(object):
                                        ctypes.c_void_p(blocks.data_ptr()), n, ctypes.c_void_p(crc_out.data_ptr()))
         self._check(rc, "xm_bgzf_crc32_dev")
 
+    def bgzf_deflate_dev(self, inp, blocks, comp, clen, status, work, stream=None):
+        """Payloads deflated on the GPU (xm_bgzf_deflate_dev): inp = uint8 device tensor holding the payloads (block b's: isize bytes
+        at out_off, any alignment; 15 readable bytes behind the last), blocks = device tensor holding a BGZF_BLOCK array (cdata_off /
+        cdata_len: where the stream goes in comp, 16-byte aligned, and how much room there is, at least isize + 5), comp = uint8 device
+        tensor, clen / status = int32 tensors with one entry per block, work = uint8 device tensor of bgzf_deflate_work_bytes() bytes
+        (less makes the launch narrower).  Asynchronous."""
+        n = blocks.numel() * blocks.element_size() // 24
+        rc = self._L.xm_bgzf_deflate_dev(self._h, self._stream_handle(stream), ctypes.c_void_p(inp.data_ptr()),
+                                         ctypes.c_void_p(blocks.data_ptr()), n, ctypes.c_void_p(comp.data_ptr()),
+                                         ctypes.c_void_p(clen.data_ptr()), ctypes.c_void_p(status.data_ptr()),
+                                         ctypes.c_void_p(work.data_ptr()), work.numel() * work.element_size())
+        self._check(rc, "xm_bgzf_deflate_dev")
+
+    def bgzf_compress(self, data, payload=0):
+        """bytes-like or uint8 array -> numpy uint8 array of complete BGZF members, `payload` bytes of data each (0 = 65280), deflated
+        and framed on the GPU (xm_bgzf_compress).  Append BGZF_EOF to make it a file.  Blocking."""
+        data = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data, dtype=np.uint8)
+        n, p = int(data.shape[0]), int(payload) if payload else BGZF_DEFLATE_MAX_ISIZE
+        if not 64 <= p <= BGZF_DEFLATE_MAX_ISIZE:
+            raise ValueError("payload %d: 64 .. %d, or 0" % (p, BGZF_DEFLATE_MAX_ISIZE))
+        out = np.empty(bgzf_compress_bound(n, p), dtype=np.uint8)
+        got = ctypes.c_uint64()
+        rc = self._L.xm_bgzf_compress(self._h, _np_ptr(data) if n else None, n, p, _np_ptr(out) if out.shape[0] else None,
+                                      out.shape[0], ctypes.byref(got))
+        self._check(rc, "xm_bgzf_compress")
+        return out[:got.value]
+
     @_one_call_per_context
     def workspace_release(self, stream):
         """Call before destroying a stream the compaction calls were issued on while this context lives on."""
@@ -768,6 +799,18 @@ BGZF_TAGS_AS_XS = ord("X") | ord("A") << 8 | ord("S") << 16
 BGZF_TAGS_AS_ZS = ord("Z") | ord("A") << 8 | ord("S") << 16
 BGZF_TAGS_NM_XS = ord("X") | ord("N") << 8 | ord("M") << 16 | 1 << 24
 BGZF_COMP_PAD = 1024
+BGZF_DEFLATE_MAX_ISIZE = 65280                                      # XMB_DEFLATE_MAX_ISIZE
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")     # the empty member that ends a file
+
+
+def bgzf_deflate_work_bytes():
+    """Device scratch xm_bgzf_deflate_dev wants for its widest launch (xm_bgzf_deflate_work_bytes)."""
+    return int(lib().xm_bgzf_deflate_work_bytes())
+
+
+def bgzf_compress_bound(n, payload=BGZF_DEFLATE_MAX_ISIZE):
+    """XMB_COMPRESS_BOUND: bytes Context.bgzf_compress never exceeds for n bytes of data."""
+    return n + 31 * ((n + payload - 1) // payload)
 
 
 def bgzf_index(data, start=0, max_out=1 << 62, cap=None, prefix=False):

@@ -15,7 +15,7 @@ CSRC = os.path.join(PKG, "csrc")
 HIP_LIB = os.path.join(PKG, "libxenomapper_hip.so")
 HOST_LIB = os.path.join(PKG, "libxenomapper_host.so")
 
-HIP_SOURCES = ["xm_kernels.hip", "xm_api.hip", "xm_strip.hip", "xm_inflate.hip", "xm_bamdev.hip"]
+HIP_SOURCES = ["xm_kernels.hip", "xm_api.hip", "xm_strip.hip", "xm_inflate.hip", "xm_deflate.hip", "xm_bamdev.hip"]
 HOST_SOURCES = ["xm_sam.cpp", "xm_bam.cpp"]
 
 
@@ -35,14 +35,14 @@ def _stale(target, sources):
 
 def build_hip(force=False, verbose=False):
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
-    deps = srcs + [os.path.join(CSRC, "xm_kernels.h"), os.path.join(CSRC, "xm_inflate_core.h"),
+    deps = srcs + [os.path.join(CSRC, "xm_kernels.h"), os.path.join(CSRC, "xm_inflate_core.h"), os.path.join(CSRC, "xm_deflate_core.h"),
                    os.path.join(CSRC, "xm_bamrec.h"), os.path.join(CSRC, "xm_fmtg.h"), os.path.join(CSRC, "xm_pinned.h"), os.path.join(CSRC, "xm_gather.h"), os.path.join(CSRC, "xm_slot.h"),
                    os.path.join(REPO, "include", "xenomapper_hip.h"), os.path.join(REPO, "include", "xenomapper_strip.h"),
                    os.path.join(REPO, "include", "xenomapper_bgzf.h")]
     if not force and not _stale(HIP_LIB, deps):
         return HIP_LIB
     # XENOMAPPER_HIPCC_FLAGS: extra flags for tuning builds (e.g. -DXM_CIGAR_BLOCK=256); not used by the tests
-    # One object per source, compiled side by side (the five translation units share no device code), objects kept under
+    # One object per source, compiled side by side (the translation units share no device code), objects kept under
     # build/obj and reused while neither their source nor any header is newer; then one link.
     flags = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-I", os.path.join(REPO, "include")] + \
         os.environ.get("XENOMAPPER_HIPCC_FLAGS", "").split()
