@@ -25,9 +25,9 @@
 extern "C" {
 #endif
 
-#define XMB_ABI_VERSION 5   /* 2: xm_bamdev_fetch_bins; f and B:f fields printed on the device.  3: raw1 / raw2 exist from the
+#define XMB_ABI_VERSION 6   /* 2: xm_bamdev_fetch_bins; f and B:f fields printed on the device.  3: raw1 / raw2 exist from the
                                first xm_bamdev_fetch_raw on (xm_bamdev_raw).  4: xm_bamdev_fetch_bins_bam.  5: xm_bgzf_deflate_dev,
-                               xm_bgzf_compress */
+                               xm_bgzf_compress.  6: xm_bamdev_fetch_bins_bamz */
 
 /* One BGZF block of the compressed image (24 bytes; the layout the kernels read). */
 typedef struct {
@@ -275,6 +275,18 @@ int xm_bamdev_fetch_bins(xm_bamdev *b, int slot, uint64_t n_records, int paired,
  * There is no status 1: a binary64 field is bytes like any other here. */
 int xm_bamdev_fetch_bins_bam(xm_bamdev *b, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload,
                              int32_t ref_shift, xm_bamdev_bins *out);
+/* (f) the same six outputs as ordinary, COMPRESSED BAM (XMB_ABI_VERSION 6): arguments, result, records and their order per bin as
+ * (e), but every member holds what xm_bgzf_deflate_dev makes of its payload -- one dynamic-Huffman block, or one stored block where
+ * that is not shorter -- between the same 18 header bytes (BSIZE = the stream's bytes + 25) and CRC-32 / ISIZE.  Every member but a
+ * bin's last holds exactly block_payload record bytes, none is longer than 65280 + 5 + 26 bytes; bin b's range is a whole number of
+ * complete members, none when the bin has no wanted unit; the bytes of a bin are those of xm_bgzf_compress on its records.
+ * status 0: on its way (xm_bamdev_raw_wait); 2: does not fit the slot's buffers -- decided before anything is written, by (e)'s
+ * bound (payload + 31 per member), which a deflated member never exceeds.  The call waits for the encoder (the members' places are
+ * the scan of their lengths): bin_off is final when it returns.  A member the encoder declines is XM_ERR_HIP (xm_bamdev_last_error).
+ * The slot's first call makes the buffers only this route needs -- the payloads, a place per member's stream, and the encoder's
+ * scratch (xm_bgzf_deflate_work_bytes()) --: XM_ERR_OOM when they cannot be made; xm_bamdev_destroy frees them. */
+int xm_bamdev_fetch_bins_bamz(xm_bamdev *b, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload,
+                              int32_t ref_shift, xm_bamdev_bins *out);
 /* the copies run on a stream of their own; this blocks until the one asked for last has arrived (any thread) */
 int xm_bamdev_raw_wait(xm_bamdev *b, int slot);
 /* the fused main loop on the slot's columns (as xm_strip_classify) */

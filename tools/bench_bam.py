@@ -73,11 +73,15 @@ def tiled_bam(src, dst, copies, aligned=True, level=6):
     return len(raw) - at
 
 
-def run(copies=4000, threads=0, workdir="/dev/shm", cigar_scores=False, single_end=False, to_files=False, bam_out=False):
+def run(copies=4000, threads=0, workdir="/dev/shm", cigar_scores=False, single_end=False, to_files=False, bam_out=False, compress=False):
     """One warm-up and one timed pass over the tiled fixtures; returns the result record (also bench.py's `e2e.bam`).
     cigar_scores: the --cigar_scores plugin (AS made of NM + CIGAR) instead of the AS / XS tags.  single_end: the files as
     single-end input, as the command line runs it: the skipping walk (every run of equal names yields its first record).
-    bam_out: output_format="bam" -- the records as they stand, gathered and BGZF-framed on the device, instead of their SAM text."""
+    bam_out: output_format="bam" -- the records as they stand, gathered and BGZF-framed on the device, instead of their SAM text;
+    compress (with bam_out): bam_compress=True -- every member deflated on the device as well.  BAM outputs: `out_bytes` = the
+    members written in the timed pass (what crossed the link; without the headers and end-of-file markers)."""
+    if compress and not bam_out:
+        raise ValueError("compress needs bam_out")
     import types
     a = types.SimpleNamespace(copies=copies, threads=threads, dir=workdir)
     from xenomapper_amd import _host, xenomapper as xm
@@ -91,6 +95,8 @@ def run(copies=4000, threads=0, workdir="/dev/shm", cigar_scores=False, single_e
     out_paths = [os.path.join(a.dir, "xm_bam_out_%s_%d.%s" % (k, os.getpid(), "bam" if bam_out else "sam")) for k in names] if to_files else []
     sinks = {k: open(os.devnull, "wt") for k in names}
     fmt = {"output_format": "bam"} if bam_out else {}
+    if compress:
+        fmt["bam_compress"] = True
     try:
         xm.default_context()
         first = None
@@ -105,7 +111,9 @@ def run(copies=4000, threads=0, workdir="/dev/shm", cigar_scores=False, single_e
             el = time.perf_counter() - t0
             first = el if first is None else first
         units = sum(counts.values())
-        return {"metric": "end-to-end %s/s (BAM in, six %s files out)" % ("reads" if single_end else "read-pairs", "BAM" if bam_out else "SAM"), "value": units / el,
+        extra = {"out_bytes": int(xm.LAST_FILE_PROFILE.get("bam_out_bytes", 0)), "compress": bool(compress)} if bam_out else {}
+        return {"metric": "end-to-end %s/s (BAM in, six %s files out)" % ("reads" if single_end else "read-pairs",
+                                                                          ("compressed BAM" if compress else "BAM") if bam_out else "SAM"), "value": units / el, **extra,
                 "plugin": "get_cigarbased_AS_tag" if cigar_scores else "get_tag", "units": units, "seconds": el, "first_run_seconds": first, "bam_bytes": size, "bam_GBps": size / el / 1e9,
                 "threads": a.threads or _host.lib().xmh_default_threads(),
                 "phases": {k: round(v, 4) for k, v in xm.LAST_FILE_PROFILE.items()}}
@@ -126,8 +134,11 @@ def main():
     ap.add_argument("--single_end", action="store_true")
     ap.add_argument("--files", action="store_true", help="six real output files in --dir instead of /dev/null")
     ap.add_argument("--bam-out", action="store_true", help="BAM outputs (records framed on the device) instead of SAM text")
+    ap.add_argument("--compress", action="store_true", help="with --bam-out: compressed BAM (every member deflated on the device)")
     a = ap.parse_args()
-    print(json.dumps(run(a.copies, a.threads, a.dir, a.cigar_scores, a.single_end, a.files, a.bam_out)))
+    if a.compress and not a.bam_out:
+        ap.error("--compress needs --bam-out")
+    print(json.dumps(run(a.copies, a.threads, a.dir, a.cigar_scores, a.single_end, a.files, a.bam_out, a.compress)))
 
 
 if __name__ == "__main__":

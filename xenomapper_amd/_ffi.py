@@ -175,6 +175,7 @@ def lib():
         "xm_bamdev_fetch_text": ([P, I, U64, I, ctypes.c_uint32, P], I),
         "xm_bamdev_fetch_bins": ([P, I, U64, I, ctypes.c_uint32, P], I),
         "xm_bamdev_fetch_bins_bam": ([P, I, U64, I, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, P], I),
+        "xm_bamdev_fetch_bins_bamz": ([P, I, U64, I, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, P], I),
         "xm_bamdev_classify": ([P, I, I, U64, I32, ctypes.POINTER(P), ctypes.POINTER(P), P, P], I),
         "xm_bamdev_columns": ([P, I, U64, P, P, P, P, P], I),
         "xm_bamdev_cigar_columns": ([P, I, I, U64, P, P, P, P, U64, ctypes.POINTER(ctypes.c_uint64)], I),
@@ -202,7 +203,7 @@ EXPORTED = ("xm_abi_version", "xm_strerror", "xm_last_hip_error", "xm_ctx_create
             "xm_strip_classify", "xm_strip_fetch_bins", "xm_strip_out_wait", "xm_strip_columns", "xm_strip_cigar_columns", "xm_strip_device_columns", "xm_strip_last_error",
             "xm_bgzf_index", "xm_bgzf_index_prefix", "xm_bgzf_inflate_dev", "xm_bgzf_inflate_walk_dev", "xm_bgzf_crc32_dev", "xm_bgzf_strerror",
             "xm_bgzf_deflate_work_bytes", "xm_bgzf_deflate_dev", "xm_bgzf_compress",
-            "xm_bamdev_create", "xm_bamdev_destroy", "xm_bamdev_reserve", "xm_bamdev_staging", "xm_bamdev_run", "xm_bamdev_raw_wait", "xm_bamdev_fetch_raw", "xm_bamdev_raw", "xm_bamdev_fetch_wanted", "xm_bamdev_fetch_text", "xm_bamdev_fetch_bins", "xm_bamdev_fetch_bins_bam", "xm_bamdev_set_refs", "xm_bamdev_upload", "xm_bamdev_classify",
+            "xm_bamdev_create", "xm_bamdev_destroy", "xm_bamdev_reserve", "xm_bamdev_staging", "xm_bamdev_run", "xm_bamdev_raw_wait", "xm_bamdev_fetch_raw", "xm_bamdev_raw", "xm_bamdev_fetch_wanted", "xm_bamdev_fetch_text", "xm_bamdev_fetch_bins", "xm_bamdev_fetch_bins_bam", "xm_bamdev_fetch_bins_bamz", "xm_bamdev_set_refs", "xm_bamdev_upload", "xm_bamdev_classify",
             "xm_bamdev_columns", "xm_bamdev_cigar_columns", "xm_bamdev_last_error")
 
 
@@ -1208,6 +1209,12 @@ class BamDev(_FrontEnd):
         raw_wait and until the next run on the slot).  block_payload: record bytes per member (0: 65280); ref_shift: added to the
         reference ids of file 2's records in `unresolved`.  status 2: more bytes than the slot's buffers hold."""
         return self._fetch_bins("fetch_bins_bam", int(slot), int(n_records), int(bool(paired)), int(sink_mask), int(block_payload),
+                                int(ref_shift))
+
+    def fetch_bins_bamz(self, slot, n_records, paired, sink_mask, block_payload=0, ref_shift=0):
+        """fetch_bins_bam with every member deflated on the device (xm_bamdev_fetch_bins_bamz): ordinary compressed BAM.  Same
+        arguments and result; bin b's bytes are those of Context.bgzf_compress on its records.  The call waits for the encoder."""
+        return self._fetch_bins("fetch_bins_bamz", int(slot), int(n_records), int(bool(paired)), int(sink_mask), int(block_payload),
                                 int(ref_shift))
 
     def upload(self, slot, file, nbytes):

@@ -33,6 +33,7 @@
 
 #include "../../include/xenomapper_bgzf.h"
 #include "xm_bamrec.h"
+#include "xm_bgzf_pack.h"                // bgzf_pack_kernel (Z5)
 #include "xm_fmtg.h"
 #include "xm_slot.h"
 
@@ -630,6 +631,9 @@ bam_layout_kernel(const uint32_t *__restrict__ starts, uint32_t P, uint32_t n_me
 // still inside the window's buffer, which ends 64 bytes behind its last record) and stores them with one dwordx4 where they lie in
 // one member, byte by byte at a seam and at the record's end.  shift != 0: refID and next_refID -- words 1 and 6 of the record,
 // counted from the block_size word: word 1 of the first piece, word 2 of the second -- move up by it where they name a reference.
+// FRAMED = false (Z2 of xm_bamdev_fetch_bins_bamz): no frames lie between the members -- `frames` is where the bin's payload begins in
+// a buffer of payloads alone, and byte r of the bin lies at frames + r; P plays no part.
+template <bool FRAMED>
 __device__ __forceinline__ void record_to_frames(const uint8_t *__restrict__ src, uint32_t size, uint8_t *__restrict__ frames, uint32_t r, uint32_t P,
                                                  int32_t shift, uint32_t lane)
 {
@@ -640,6 +644,19 @@ __device__ __forceinline__ void record_to_frames(const uint8_t *__restrict__ src
             if (k == 16u && (int32_t)v[2] >= 0) v[2] += (uint32_t)shift;
         }
         const uint32_t at = r + k, valid = size - k < 16u ? size - k : 16u;
+        if constexpr (!FRAMED) {
+            uint8_t *dst = frames + at;
+            if (valid == 16u) {
+                *reinterpret_cast<v4u32_any *>(dst) = v;
+            } else {
+#pragma unroll
+                for (uint32_t t = 0; t < 16u; ++t) {
+                    if (t >= valid) break;
+                    dst[t] = (uint8_t)(v[t >> 2] >> (8u * (t & 3u)));
+                }
+            }
+            continue;
+        }
         uint32_t member = at / P, in = at - member * P;
         uint8_t *dst = frames + (uint64_t)member * (P + BGZF_FRAME) + BGZF_HEAD + STORED_HEAD + in;
         if (valid == 16u && in + 16u <= P) {
@@ -657,6 +674,8 @@ __device__ __forceinline__ void record_to_frames(const uint8_t *__restrict__ src
 
 // O2: a wave per (unit, record of the unit) in the order line_fill_kernel takes its lines: a paired unit is records i - 1 and i, and
 // `unresolved` takes file 1's record(s) and then file 2's.  usize / uplace: the units' payload bytes and places (G1, the size scan).
+// FRAMED = false (Z2): the records of a bin back to back from out + starts[bin] on, as the size scan placed them; layout is not read.
+template <bool FRAMED>
 __global__ void __launch_bounds__(256)
 record_fill_kernel(const uint8_t *__restrict__ raw1, const uint8_t *__restrict__ raw2, const uint32_t *__restrict__ rec_off1,
                    const uint32_t *__restrict__ rec_off2, const uint32_t *__restrict__ idx, const unsigned long long *__restrict__ off,
@@ -674,7 +693,7 @@ record_fill_kernel(const uint8_t *__restrict__ raw1, const uint8_t *__restrict__
     const uint32_t i = idx[p], files = files_of_bin(bin, sink_mask);
     if (i >= n_records || (paired && i == 0u)) return;
     const uint32_t rec = paired ? i - 1u + j : i;
-    const uint32_t frame0 = layout->frame_start[bin], frame1 = layout->frame_start[bin + 1u];
+    const uint32_t frame0 = FRAMED ? layout->frame_start[bin] : starts[bin], frame1 = FRAMED ? layout->frame_start[bin + 1u] : starts[bin + 1u];
     if (frame1 > out_cap || frame0 > frame1) return;                            // (the total was checked before the launch)
     uint32_t r = uplace[p] - starts[bin];                                       // the unit's first payload byte inside its bin
     if (r > starts[bin + 1u] - starts[bin] || size > starts[bin + 1u] - starts[bin] - r) return;
@@ -683,7 +702,7 @@ record_fill_kernel(const uint8_t *__restrict__ raw1, const uint8_t *__restrict__
         const uint32_t *ws = f ? ws2 : ws1;
         const uint32_t first = paired ? ws[i - 1u] : 0u, mine = ws[rec];
         if (mine != 0u)
-            record_to_frames((f ? raw2 : raw1) + (f ? rec_off2 : rec_off1)[rec], mine, out + frame0, r + (j ? first : 0u), P,
+            record_to_frames<FRAMED>((f ? raw2 : raw1) + (f ? rec_off2 : rec_off1)[rec], mine, out + frame0, r + (j ? first : 0u), P,
                              (f == 1u && bin == 4u) ? ref_shift : 0, lane);
         r += first + ws[i];                                                     // behind file 1's records of the unit: file 2's
     }
@@ -709,6 +728,88 @@ bam_frame_kernel(const xm_bgzf_block *__restrict__ members, const uint32_t *__re
     const uint32_t c = crc[m];
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k) { t[k] = (uint8_t)(c >> (8u * k)); t[4u + k] = (uint8_t)(len >> (8u * k)); }
+}
+
+// ---- Z: the six outputs as compressed BAM (xm_bamdev_fetch_bins_bamz): the same payloads, each member deflated -----------------------
+// O's scan and O's members, but the payloads are gathered WITHOUT frames into a buffer of their own (Z2 = O2 with FRAMED = false:
+// bin b's bytes from S_b on), member m's stream is made by xm_bgzf_deflate_dev in a slot of its own (m * slot, slot = P + 5 rounded up
+// to 16: what a stream never exceeds), and only then is it known where a member lies in the output: Z4 scans the streams' lengths + 26,
+// Z5 (bgzf_pack_kernel, xm_bgzf_pack.h) moves every stream between its header and its trailer.
+// Z1: a lane per member: its descriptor for the encoder and the CRC kernel; lane 0 leaves the bins' first members for Z4
+__global__ void __launch_bounds__(256)
+bamz_layout_kernel(const uint32_t *__restrict__ starts, uint32_t P, uint32_t slot, uint32_t n_members, BamLayout *__restrict__ layout,
+                   xm_bgzf_block *__restrict__ members)
+{
+    BamLayout l;
+    bam_layout_of(starts, P, l);
+    const uint32_t m = blockIdx.x * 256u + threadIdx.x;
+    if (m == 0u) *layout = l;
+    if (m >= n_members || m >= l.member_start[7]) return;
+    uint32_t b = 0;
+#pragma unroll
+    for (uint32_t k = 1; k < 7u; ++k) b += (l.member_start[k] <= m) ? 1u : 0u;
+    const uint32_t k = m - l.member_start[b], len = starts[b + 1u] - starts[b], left = len - k * P;
+    xm_bgzf_block d;
+    d.cdata_off = (uint64_t)m * slot; d.cdata_len = slot;
+    d.out_off = (uint64_t)starts[b] + (uint64_t)k * P;
+    d.isize = left < P ? left : P;
+    members[m] = d;
+}
+
+// Z4: where every member goes: the exclusive scan of clen[m] + 26 (18 bytes of header, 8 of trailer) over the members, in ONE workgroup
+// the way part_scan_kernel (xm_gather.h) scans the size scan's partials -- thread t sums the members [t per, (t + 1) per), per =
+// ceil(n / 256), the 256 sums are scanned in LDS, and the thread walks its members again from its base: any number of members, one
+// launch.  placed[b] = where bin b's first member lies (b = 0..6; a bin without members: where the next one's does), placed[7] = the
+// total, placed[8] = the OR of the members' status -- with XMB_DEFLATE_ERR_CAPACITY for a length no stream may have, which is then
+// set to 0 so that Z5 writes nothing but that member's frame.
+constexpr uint32_t BAMZ_PLACE_THREADS = 256;      // (members are few: 4 000 in a window of 256 MB at the default payload)
+__global__ void __launch_bounds__(BAMZ_PLACE_THREADS)
+bamz_place_kernel(const xm_bgzf_block *__restrict__ members, uint32_t *__restrict__ clen, const uint32_t *__restrict__ status, uint32_t n_members,
+                  const BamLayout *__restrict__ layout, unsigned long long *__restrict__ member_off, unsigned long long *__restrict__ placed)
+{
+    __shared__ unsigned long long sh[BAMZ_PLACE_THREADS];
+    __shared__ uint32_t any_status;
+    const uint32_t t = threadIdx.x, per = (n_members + BAMZ_PLACE_THREADS - 1u) / BAMZ_PLACE_THREADS;
+    const uint32_t a = min(t * per, n_members), e = min(a + per, n_members);
+    if (t == 0u) any_status = 0u;
+    __syncthreads();
+    unsigned long long s = 0;
+    uint32_t st = 0;
+    for (uint32_t k = a; k < e; ++k) {
+        uint32_t c = clen[k];
+        const uint32_t bad = status[k] | (c > XMB_DEFLATE_BOUND(members[k].isize) ? XMB_DEFLATE_ERR_CAPACITY : 0u);
+        if (bad) { c = 0u; clen[k] = 0u; }
+        st |= bad;
+        s += c + (BGZF_HEAD + BGZF_TAIL);
+    }
+    if (st) atomicOr(&any_status, st);
+    sh[t] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < BAMZ_PLACE_THREADS; d <<= 1) {
+        const unsigned long long x = t >= d ? sh[t - d] : 0ull;
+        __syncthreads();
+        sh[t] += x;
+        __syncthreads();
+    }
+    uint32_t first[7];
+#pragma unroll
+    for (uint32_t b = 0; b < 7u; ++b) first[b] = layout->member_start[b];
+    unsigned long long run = sh[t] - s;
+    for (uint32_t k = a; k < e; ++k) {
+        member_off[k] = run;
+#pragma unroll
+        for (uint32_t b = 0; b < 7u; ++b)
+            if (first[b] == k) placed[b] = run;
+        run += clen[k] + (BGZF_HEAD + BGZF_TAIL);
+    }
+    if (t == BAMZ_PLACE_THREADS - 1u) {
+        const unsigned long long total = sh[BAMZ_PLACE_THREADS - 1u];
+#pragma unroll
+        for (uint32_t b = 0; b < 7u; ++b)
+            if (first[b] >= n_members) placed[b] = total;
+        placed[7] = total;
+        placed[8] = any_status;
+    }
 }
 
 // ---- --cigar_scores: the records' CIGAR words as the packed CIGAR columns K1p reads (include/xenomapper_hip.h) ------------------
@@ -932,6 +1033,12 @@ struct Slot : ClassifyOut, GatherPlan {               // (xm_slot.h: the columns
     uint32_t *d_member_crc = nullptr;
     BamLayout *d_layout = nullptr;
     uint64_t member_cap = 0;
+    // compressed BAM outputs (xm_bamdev_fetch_bins_bamz), made when the first such call comes: the payloads without frames, a slot per
+    // member for its stream, the streams' lengths and status, where Z4 places the members and what it reports, the encoder's scratch
+    uint8_t *d_zpayload = nullptr, *d_zcomp = nullptr, *d_zwork = nullptr;
+    uint32_t *d_zclen = nullptr, *d_zstatus = nullptr;
+    unsigned long long *d_zoff = nullptr, *d_zplaced = nullptr, *h_zplaced = nullptr;      // placed: 8 bin starts and the status word
+    uint64_t z_payload_bytes = 0, z_comp_bytes = 0, z_member_cap = 0, z_work_bytes = 0;
     xm_bgzf_block *h_blocks = nullptr;
     xm_bgzf_walk *h_walk = nullptr;                         // per block: where its record chain starts and where its results go
     uint32_t *d_status = nullptr, *h_status = nullptr, *d_crc = nullptr, *h_crc = nullptr, *d_work = nullptr;
@@ -985,6 +1092,9 @@ void free_slot(Slot &sl)
     dfree(sl.d_raw_all); dfree(sl.d_packed_all); hfree(sl.h_packed_all);
     sl.free_units();
     dfree(sl.d_members); dfree(sl.d_member_crc); dfree(sl.d_layout); sl.member_cap = 0;
+    dfree(sl.d_zpayload); dfree(sl.d_zcomp); dfree(sl.d_zwork); dfree(sl.d_zclen); dfree(sl.d_zstatus); dfree(sl.d_zoff);
+    dfree(sl.d_zplaced); hfree(sl.h_zplaced);
+    sl.z_payload_bytes = sl.z_comp_bytes = sl.z_member_cap = sl.z_work_bytes = 0;
     hfree(sl.h_blocks); hfree(sl.h_walk); dfree(sl.d_status); hfree(sl.h_status); dfree(sl.d_crc); hfree(sl.h_crc);
     sl.release();
     sl.comp_cap = sl.raw_cap = sl.block_cap = sl.record_cap = 0;
@@ -1120,6 +1230,49 @@ static int bins_home(xm_bamdev *b, Slot &sl, uint64_t bytes)
     const int rc = Slot::send_home(b, sl.stream, sl.copy_stream, sl.ev_inflated, sl.ev_raw, sl.d_packed_all, sl.h_packed_all, bytes);
     sl.raw_issued = true;                                                   // (the buffers end 64 bytes behind out_cap)
     return rc;
+}
+
+// the members' descriptors and CRCs (both BAM gathers), for n_members and a quarter more; the slot's stream is idle
+static int ensure_members(xm_bamdev *b, Slot &sl, uint64_t n_members)
+{
+    if (n_members <= sl.member_cap) return XM_OK;
+    sl.member_cap = 0;
+    const size_t cap = (size_t)n_members + (size_t)n_members / 4 + 64;
+    XMF_TRY(dalloc(b, sl.d_members, cap)); XMF_TRY(dalloc(b, sl.d_member_crc, cap));
+    if (!sl.d_layout) XMF_TRY(dalloc(b, sl.d_layout, 1));
+    sl.member_cap = cap;
+    return XM_OK;
+}
+
+// what only the compressed gather needs, for n_members streams of `slot` bytes each; the slot's stream is idle.  A buffer that cannot
+// be made leaves its capacity at 0 (the next call tries again) and the error is the allocator's: XM_ERR_OOM.
+static int ensure_bamz(xm_bamdev *b, Slot &sl, uint64_t n_members, uint64_t slot)
+{
+    const uint64_t payload_bytes = 2 * sl.packed_stride;                    // out_cap + 64: the encoder reads up to 15 bytes behind a payload
+    if (sl.z_payload_bytes < payload_bytes) {
+        sl.z_payload_bytes = 0;
+        XMF_TRY(dalloc(b, sl.d_zpayload, (size_t)payload_bytes));
+        sl.z_payload_bytes = payload_bytes;
+    }
+    if (sl.z_comp_bytes < n_members * slot) {
+        sl.z_comp_bytes = 0;
+        const uint64_t bytes = n_members * slot + n_members * slot / 4 + 64;
+        XMF_TRY(dalloc(b, sl.d_zcomp, (size_t)bytes));
+        sl.z_comp_bytes = bytes;
+    }
+    if (sl.z_member_cap < n_members) {
+        sl.z_member_cap = 0;
+        const size_t cap = (size_t)n_members + (size_t)n_members / 4 + 64;
+        XMF_TRY(dalloc(b, sl.d_zclen, cap)); XMF_TRY(dalloc(b, sl.d_zstatus, cap)); XMF_TRY(dalloc(b, sl.d_zoff, cap));
+        sl.z_member_cap = cap;
+    }
+    if (!sl.d_zplaced) XMF_TRY(dalloc(b, sl.d_zplaced, 16));
+    if (!sl.h_zplaced) XMF_TRY(halloc(b, sl.h_zplaced, 16));
+    if (sl.z_work_bytes == 0) {
+        XMF_TRY(dalloc(b, sl.d_zwork, (size_t)xm_bgzf_deflate_work_bytes()));
+        sl.z_work_bytes = xm_bgzf_deflate_work_bytes();
+    }
+    return XM_OK;
 }
 
 extern "C" {
@@ -1759,22 +1912,72 @@ int xm_bamdev_fetch_bins_bam(xm_bamdev *b, int slot, uint64_t n_records, int pai
     out->bin_off[7] = framed;
     if (framed > job.out_cap) { memset(out->bin_off, 0, sizeof out->bin_off); out->status = 2; return XM_OK; }
     if (n_members == 0) return XM_OK;
-    if (n_members > sl.member_cap) {                                        // (the slot's stream is idle: the wait above)
-        sl.member_cap = 0;
-        const size_t cap = (size_t)n_members + (size_t)n_members / 4 + 64;
-        XMF_TRY(dalloc(b, sl.d_members, cap)); XMF_TRY(dalloc(b, sl.d_member_crc, cap));
-        if (!sl.d_layout) XMF_TRY(dalloc(b, sl.d_layout, 1));
-        sl.member_cap = cap;
-    }
+    XMF_TRY(ensure_members(b, sl, n_members));                              // (the slot's stream is idle: the wait above)
     const uint32_t nm = (uint32_t)n_members;
     bam_layout_kernel<<<(nm + 255u) / 256u, 256, 0, st>>>(job.gs + GS_STARTS, P, nm, sl.d_layout, sl.d_members);
-    record_fill_kernel<<<((paired ? 2u : 1u) * n_units + 3u) / 4u, 256, 0, st>>>(
+    record_fill_kernel<true><<<((paired ? 2u : 1u) * n_units + 3u) / 4u, 256, 0, st>>>(
         sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, sl.d_idx, job.d_off, n_units, n, paired ? 1 : 0, sink_mask,
         sl.pf[0].d_wsize, sl.pf[1].d_wsize, sl.d_usize, sl.d_uplace, job.gs + GS_STARTS, sl.d_layout, P, ref_shift, sl.d_packed_all, (uint32_t)job.out_cap);
     const int rc = xm_bgzf_crc32_dev(b->ctx, st, sl.d_packed_all, sl.d_members, n_members, sl.d_member_crc);
     if (rc != XM_OK) return rc;
     bam_frame_kernel<<<(nm + 255u) / 256u, 256, 0, st>>>(sl.d_members, sl.d_member_crc, nm, sl.d_packed_all, (uint32_t)job.out_cap);
     return bins_home(b, sl, framed);
+}
+
+int xm_bamdev_fetch_bins_bamz(xm_bamdev *b, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload,
+                              int32_t ref_shift, xm_bamdev_bins *out)
+{
+    if (!b || slot < 0 || slot > 1 || !out) return XM_ERR_INVALID_ARG;
+    Slot &sl = b->slot[slot];
+    if (!sl.can_fetch(n_records)) return XM_ERR_INVALID_ARG;
+    const uint32_t P = block_payload ? block_payload : XMB_DEFLATE_MAX_ISIZE;
+    if (P < 64u || P > XMB_DEFLATE_MAX_ISIZE) return XM_ERR_INVALID_ARG;
+    BinsJob job;
+    XMF_TRY(begin_bins(b, sl, n_records, paired, sink_mask, false, out, job));
+    if (job.n_units == 0) return XM_OK;
+    hipStream_t st = sl.stream;
+    const uint32_t n = job.n, n_units = job.n_units;
+    Placed at;
+    XMF_TRY(place_bins(b, sl, job, paired, sink_mask, at));
+    if (at.total > job.out_cap) { out->status = 2; return XM_OK; }
+    // Whether the stream fits is decided here, by the stored route's sums: a deflated member is never longer than its stored form
+    // (XMB_DEFLATE_BOUND), so what Z5 writes lies inside the bytes these sums count.
+    uint64_t framed = 0, n_members = 0;
+    for (int k = 0; k < 7; ++k) {
+        if (at.starts[k + 1] < at.starts[k]) return XM_ERR_HIP;
+        const uint64_t len = at.starts[k + 1] - at.starts[k], members = (len + P - 1u) / P;
+        framed += len + members * BGZF_FRAME;
+        n_members += members;
+    }
+    if (framed > job.out_cap) { out->status = 2; return XM_OK; }
+    if (n_members == 0) return XM_OK;
+    const uint32_t slot_bytes = (P + STORED_HEAD + 15u) & ~15u;
+    XMF_TRY(ensure_members(b, sl, n_members));                              // (the slot's stream is idle: the wait above)
+    XMF_TRY(ensure_bamz(b, sl, n_members, slot_bytes));
+    const uint32_t nm = (uint32_t)n_members;
+    bamz_layout_kernel<<<(nm + 255u) / 256u, 256, 0, st>>>(job.gs + GS_STARTS, P, slot_bytes, nm, sl.d_layout, sl.d_members);
+    record_fill_kernel<false><<<((paired ? 2u : 1u) * n_units + 3u) / 4u, 256, 0, st>>>(
+        sl.pf[0].d_raw, sl.pf[1].d_raw, sl.pf[0].v_rec_off, sl.pf[1].v_rec_off, sl.d_idx, job.d_off, n_units, n, paired ? 1 : 0, sink_mask,
+        sl.pf[0].d_wsize, sl.pf[1].d_wsize, sl.d_usize, sl.d_uplace, job.gs + GS_STARTS, sl.d_layout, P, ref_shift, sl.d_zpayload, (uint32_t)job.out_cap);
+    int rc = xm_bgzf_deflate_dev(b->ctx, st, sl.d_zpayload, sl.d_members, n_members, sl.d_zcomp, sl.d_zclen, sl.d_zstatus, sl.d_zwork,
+                                 sl.z_work_bytes);
+    if (rc == XM_OK) rc = xm_bgzf_crc32_dev(b->ctx, st, sl.d_zpayload, sl.d_members, n_members, sl.d_member_crc);
+    if (rc != XM_OK) return rc;
+    bamz_place_kernel<<<1, BAMZ_PLACE_THREADS, 0, st>>>(sl.d_members, sl.d_zclen, sl.d_zstatus, nm, sl.d_layout, sl.d_zoff, sl.d_zplaced);
+    bgzf_pack_kernel<<<nm, 64, 0, st>>>(sl.d_zcomp, sl.d_members, sl.d_zclen, sl.d_member_crc, reinterpret_cast<const uint64_t *>(sl.d_zoff), nm,
+                                        sl.d_packed_all);
+    XMF_HIP(b, hipMemcpyAsync(sl.h_zplaced, sl.d_zplaced, 9 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    XMF_TRY(wait_for(b, st, sl.ev_wait));
+    if (sl.h_zplaced[8] != 0ull || sl.h_zplaced[7] > framed) {
+        char text[160];
+        snprintf(text, sizeof text, "xm_bamdev_fetch_bins_bamz: members were not encoded (status bits 0x%llx: %s), %llu bytes placed of at most %llu",
+                 sl.h_zplaced[8], xm_bgzf_strerror((uint32_t)sl.h_zplaced[8]), sl.h_zplaced[7], (unsigned long long)framed);
+        std::lock_guard<std::mutex> hold(b->error_lock);
+        b->last_error = text;
+        return XM_ERR_HIP;
+    }
+    for (int k = 0; k < 8; ++k) out->bin_off[k] = sl.h_zplaced[k];
+    return bins_home(b, sl, sl.h_zplaced[7]);
 }
 
 int xm_bamdev_raw_wait(xm_bamdev *b, int slot)

@@ -1610,11 +1610,13 @@ class _GpuBamFile(object):
         self.reader.close()
 
 
-def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_threads=0, bam=False, starts=None, out_bam=False):
+def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_threads=0, bam=False, starts=None, out_bam=False,
+               bam_compress=False):
     """The three main loops on two SAM (or BAM) *files*: same results as _run(mode, getReadPairs(...)), with the
     text work done by the C++ stripper / writer.  Falls back to the Python reader when the input is not ASCII.
     out_bam: the sinks (_BamSink, one per bin) get the units' alignment records as BGZF members instead of their SAM text -- the
-    windows the device takes gathered and framed there (xm_bamdev_fetch_bins_bam), the others assembled by _bam_records_of."""
+    windows the device takes gathered and framed there (xm_bamdev_fetch_bins_bam; bam_compress: gathered, deflated and framed there,
+    xm_bamdev_fetch_bins_bamz), the others assembled by _bam_records_of."""
     from . import _host
     ctx = default_context()
     paired = mode != _ffi.MODE_SE
@@ -1822,14 +1824,17 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                 if out_bam:
                     # the six outputs as BAM: the records as they stand, gathered and framed on the device -- nothing is printed
                     if bam_out_on_device:
-                        bins = bamdev.fetch_bins_bam(which, blk.n, paired, mask, 0, ref_shift)
+                        # (bam_compress: every member deflated on the device as well -- ordinary compressed BAM)
+                        fetch = bamdev.fetch_bins_bamz if bam_compress else bamdev.fetch_bins_bam
+                        bins = fetch(which, blk.n, paired, mask, 0, ref_shift)
                         if bins[0] == 0:
                             blk.bins = bins
                     # (status 2 -- more bytes than the slot's buffers hold -- or XENOMAPPER_GPU_BAM_BINS=0: the packed records
                     # come back and the host assembles)
                     if blk.bins is None:
                         blk.packed = bamdev.fetch_wanted(which, blk.n, paired, mask)
-                    key = "bam_windows_device_bam_bins" if blk.bins is not None else "bam_windows_host_bam"
+                    key = (("bam_windows_device_bamz_bins" if bam_compress else "bam_windows_device_bam_bins") if blk.bins is not None
+                           else "bam_windows_host_bam")
                 else:
                     if bam_bins_on_device[0]:
                         # the six outputs themselves, gathered on the device: what comes back is what the sinks get
@@ -2026,6 +2031,8 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                 for b in range(6):
                     if sinks[b] and boff[b + 1] > boff[b]:
                         piece = text[boff[b]:boff[b + 1]]
+                        if out_bam:                              # what crossed the link is what is written: the framed members
+                            prof["bam_out_bytes"] = prof.get("bam_out_bytes", 0) + int(boff[b + 1] - boff[b])
                         with prof("emit"):
                             done = _emit_into_file(parser, paired, b, None, sinks[b], ahead, ahead_pool, ready=piece)
                         if not done:
@@ -2039,6 +2046,7 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
                         seg = seg[seg < limit]
                     with prof("emit"):
                         data = _bgzf_frame(_bam_records_of(seg, paired, b, block.bam_src[0], block.bam_src[1], ref_shift), 1)
+                    prof["bam_out_bytes"] = prof.get("bam_out_bytes", 0) + len(data)
                     with prof("write"):
                         _write_bytes(sinks[b], data)
             for b in (range(6) if (distinct and not out_bam and (ready is None or limit is not None)) else ()):
@@ -2212,7 +2220,7 @@ def _finish_in_python(mode, path1, path2, pos, sinks, min_score, tag_func, skip_
 def classify_sam_files(primary_sam, secondary_sam, primary_specific=sys.stdout, secondary_specific=None,
                        primary_multi=None, secondary_multi=None, unassigned=None, unresolved=None, paired=False,
                        conservative=False, min_score=float("-inf"), tag_func=get_tag, skip_repeated_reads=None,
-                       n_threads=0, bam=False, output_format="sam"):
+                       n_threads=0, bam=False, output_format="sam", bam_compress=False):
     """File-level entry point: classify two SAM files (paths) whose headers the caller has already dealt with
     (process_headers).  Equivalent to main_*(getReadPairs(open(primary_sam), open(secondary_sam), ...)) after the
     header lines, but parses and writes through the C++ stripper.  tag_func must be one of the three built-in
@@ -2222,9 +2230,14 @@ def classify_sam_files(primary_sam, secondary_sam, primary_specific=sys.stdout, 
     alignment records as they stand in the inputs, in BGZF members of stored blocks framed on the GPU (what `samtools view -u`
     writes), and the end-of-file marker after a run that succeeded.  The sinks are binary handles, or text handles with a
     `.buffer`, one per bin.  Refused before anything is written: SAM inputs and shared sinks (ValueError), a sink without bytes
-    (TypeError), no GPU BAM front end (RuntimeError)."""
+    (TypeError), no GPU BAM front end (RuntimeError).
+    bam_compress=True (output_format="bam" only, else ValueError): ordinary compressed BAM -- every member deflated on the GPU
+    (xm_bamdev_fetch_bins_bamz: one dynamic-Huffman block, or a stored one where that is not shorter); windows the host assembles
+    are deflated by zlib at level 1, as they are without it.  Default False: the stored members, byte for byte as before."""
     if output_format not in ("sam", "bam"):
         raise ValueError("output_format must be 'sam' or 'bam'")
+    if bam_compress and output_format != "bam":
+        raise ValueError("bam_compress needs output_format='bam'")
     if tag_func not in (get_tag, get_tag_with_ZS_as_XS, get_cigarbased_AS_tag):
         raise ValueError("classify_sam_files needs a built-in tag_func; use main_* for custom plugins")
     if skip_repeated_reads is None:
@@ -2236,7 +2249,7 @@ def classify_sam_files(primary_sam, secondary_sam, primary_specific=sys.stdout, 
             raise ValueError("BAM outputs need BAM inputs (bam=True)")
         sinks = _bam_sinks(sinks)
         counts = _run_files(mode, primary_sam, secondary_sam, sinks, min_score, tag_func, skip_repeated_reads, n_threads, bam,
-                            out_bam=True)
+                            out_bam=True, bam_compress=bool(bam_compress))
         for sink in sinks:                                           # (not after an exception: a file without the marker is truncated)
             if sink:
                 _write_bytes(sink, BGZF_EOF)
@@ -2353,6 +2366,7 @@ def command_line_interface(*args, **kw):
                                 default=sys.stdout if flag == "primary_specific" else None, help=text)
     # (not in --help: its text is the reference's, byte for byte; README documents the flag)
     parser.add_argument("--bam_outputs", action="store_true", help=argparse.SUPPRESS)
+    parser.add_argument("--bam_compress", action="store_true", help=argparse.SUPPRESS)
     ns = parser.parse_args(*args, **kw)
     if ns.version:
         print(__version__)
@@ -2363,6 +2377,8 @@ def command_line_interface(*args, **kw):
         sys.exit(1)
     if ns.bam_outputs and (not ns.primary_bam or not ns.secondary_bam):
         parser.error("--bam_outputs needs --primary_bam and --secondary_bam")
+    if ns.bam_compress and not ns.bam_outputs:
+        parser.error("--bam_compress needs --bam_outputs")
     return ns
 
 
@@ -2383,7 +2399,8 @@ def main(argv=None):
         process_headers(args.primary_bam, args.secondary_bam, bam=True, output_format="bam", **sinks)
         category_counts = classify_sam_files(args.primary_bam.name, args.secondary_bam.name, paired=args.paired,
                                              conservative=args.conservative, min_score=args.min_score, tag_func=tag_func,
-                                             skip_repeated_reads=skip_repeated, bam=True, output_format="bam", **sinks)
+                                             skip_repeated_reads=skip_repeated, bam=True, output_format="bam",
+                                             bam_compress=args.bam_compress, **sinks)
         output_summary(category_counts=category_counts, outfile=sys.stderr)
         for sink in sinks.values():
             if sink:
