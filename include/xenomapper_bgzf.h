@@ -37,7 +37,15 @@ typedef struct {
     uint32_t isize;         /* inflated size from the member trailer (<= 65536)                                   */
 } xm_bgzf_block;
 
-/* per-block status written by xm_bgzf_inflate_dev: 0 = ok, else the decoder's error (xm_bgzf_strerror) */
+/* per-block status written by xm_bgzf_inflate_dev: 0 = ok, else the decoder's error (xm_bgzf_strerror):
+ *    1 reserved block type            2 stored block: LEN / NLEN mismatch      3 bad code-length sequence, HLIT > 286, HDIST > 30
+ *    4 over-subscribed Huffman code   5 no end-of-block code                   6 bits that match no code
+ *    7 distance beyond the block's first byte                                  8 more output than ISIZE
+ *    9 the stream runs past its cdata_len bytes                               10 the stream ends before ISIZE bytes
+ *   11 length symbol 286 / 287       12 step guard (unreachable)
+ *   13 incomplete Huffman code in a dynamic block: the code-length code always; a literal/length or distance code unless it is
+ *      no code at all or a single code of one bit (what zlib accepts, so what encoders send).
+ * The decoder accepts a member exactly when zlib's inflate accepts its stream and produces ISIZE bytes from all cdata_len bytes. */
 #define XMB_OK 0
 
 /*
@@ -62,6 +70,8 @@ int xm_bgzf_index_prefix(const uint8_t *image, uint64_t len, uint64_t start, uin
  * work: 4 bytes of device scratch (the launch's block counter; zeroed by the call).
  * No input makes the decoder read outside [comp, last block + XMB_COMP_PAD) or write outside a block's own
  * [out_off, out_off + isize): a damaged stream ends with a non-zero status.
+ * A block of isize 0 is not decoded: its status is 0 and none of its bytes is read (the end-of-file member is the one such member
+ * BGZF writers make); whether its stream is a valid empty one is not checked.
  */
 #define XMB_COMP_PAD 1024u
 int xm_bgzf_inflate_dev(xm_ctx *ctx, void *stream, const uint8_t *comp, const xm_bgzf_block *blocks, uint64_t n_blocks,

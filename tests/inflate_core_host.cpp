@@ -5,6 +5,12 @@
 // cross-lane cooperation of GS > 1 lanes -- that is tests/test_inflate_gpu.py on the GPU.
 //   usage: inflate_core_host <file.bam|file.gz-with-BGZF-blocks> ...   (every BGZF block against zlib)
 //          inflate_core_host --fuzz N seed                            (random inputs deflated by zlib at several levels / strategies)
+//          inflate_core_host --streams IN OUT                         (hand-made streams, tests/deflate_asm.py: statuses and bytes out)
+#include <stdint.h>
+// what the decoder went through (the --streams mode reports it): blocks begun per type, codes beyond the two root tables
+static uint32_t g_blocks[4], g_long_lit, g_long_dist;
+#define XMI_STAT_BLOCK(type) (++g_blocks[(type) & 3u])
+#define XMI_STAT_LONG_CODE(root_bits) ((root_bits) == 10u ? ++g_long_lit : (root_bits) == 8u ? ++g_long_dist : 0u)
 #include "../xenomapper_amd/csrc/xm_inflate_core.h"
 
 #include <zlib.h>
@@ -133,10 +139,47 @@ static int check_file(const char *path)
     return bad;
 }
 
+// IN: u32 count, then per stream u32 cdata bytes, u32 ISIZE, u32 output alignment (address modulo 16), u32 input shift, the cdata.
+// OUT: per stream i32 status, u32 n = 64 + ISIZE + 64, n bytes: the output with the 64 guard bytes in front of it and behind it
+// (0xEE where the decoder wrote nothing).  Zeros follow every stream in the decoder's input.  The verdicts are the caller's.
+static int streams(const char *in_path, const char *out_path)
+{
+    FILE *fi = fopen(in_path, "rb"), *fo = fopen(out_path, "wb");
+    if (!fi || !fo) { perror(fi ? out_path : in_path); return 1; }
+    uint32_t count = 0;
+    if (fread(&count, 4, 1, fi) != 1) return 1;
+    for (uint32_t k = 0; k < count; ++k) {
+        uint32_t h[4];
+        if (fread(h, 4, 4, fi) != 4) { fprintf(stderr, "%s: cut inside stream %u\n", in_path, k); return 1; }
+        const uint32_t clen = h[0], isize = h[1], align = h[2] & 15u, shift = h[3];
+        std::vector<uint8_t> comp(shift + clen + 2048, 0);
+        if (clen && fread(comp.data() + shift, 1, clen, fi) != clen) { fprintf(stderr, "%s: cut inside stream %u\n", in_path, k); return 1; }
+        void *mem = nullptr;
+        const size_t room = 64 + 16 + (size_t)isize + 64;
+        if (posix_memalign(&mem, 64, room) != 0) return 1;
+        uint8_t *out = static_cast<uint8_t *>(mem);
+        memset(out, 0xEE, room);
+        static xmi::ChainMem cm;
+        xmi::Chain<1> ch;
+        const int32_t rc = ch.run(&cm, 0u, comp.data(), shift, clen, out, 64 + align, isize);
+        const uint32_t n = 64 + isize + 64;
+        fwrite(&rc, 4, 1, fo);
+        fwrite(&n, 4, 1, fo);
+        fwrite(out + align, 1, n, fo);
+        free(mem);
+    }
+    fclose(fi);
+    if (fclose(fo) != 0) return 1;
+    printf("streams: %u blocks: %u stored %u fixed %u dynamic, %u long literal/length codes, %u long distance codes\n", count,
+           g_blocks[0], g_blocks[1], g_blocks[2], g_long_lit, g_long_dist);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     int bad = 0;
     for (int a = 1; a < argc; ++a) {
+        if (std::string(argv[a]) == "--streams" && a + 2 < argc) { bad += streams(argv[a + 1], argv[a + 2]); a += 2; continue; }
         if (std::string(argv[a]) == "--fuzz" && a + 2 < argc) { bad += fuzz(atoi(argv[a + 1]), (unsigned)atoi(argv[a + 2])); a += 2; }
         else bad += check_file(argv[a]);
     }

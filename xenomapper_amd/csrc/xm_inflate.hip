@@ -335,6 +335,7 @@ const char *xm_bgzf_strerror(uint32_t s)
     case xmi::ERR_IN: return "DEFLATE stream runs past the block's compressed bytes";
     case xmi::ERR_SHORT: return "DEFLATE stream ends before ISIZE bytes";
     case xmi::ERR_LENSYM: return "invalid length symbol";
+    case xmi::ERR_INCOMPLETE: return "incomplete Huffman code in a dynamic block";
     case XMB_DEFLATE_ERR_ISIZE: return "deflate: more payload bytes than a block may hold (65280)";
     case XMB_DEFLATE_ERR_CAPACITY: return "deflate: the stream's place is smaller than the payload + 5 bytes";
     case XMB_DEFLATE_ERR_ALIGN: return "deflate: the stream's place is not 16-byte aligned";

@@ -48,14 +48,16 @@ enum : int {
     ERR_LENGTHS = 3,        // bad code-length sequence (repeat with no previous length, too many lengths)
     ERR_OVERSUB = 4,        // over-subscribed Huffman code
     ERR_NO_EOB = 5,         // no end-of-block code
-    ERR_CODE = 6,           // bits that match no code
-    ERR_DIST = 7,           // distance beyond the start of the block, or distance code 30 / 31
+    ERR_CODE = 6,           // bits that match no code: possible only where a code may be incomplete -- the fixed distance code
+                            // (built over its 30 symbols: the bits of codes 30 / 31 match nothing), a lone one-bit code, no code at all
+    ERR_DIST = 7,           // distance beyond the start of the block
     ERR_OUT = 8,            // more output than the block's ISIZE
     ERR_IN = 9,             // ran past the end of the compressed data
     ERR_SHORT = 10,         // stream ended with fewer bytes than ISIZE
     ERR_LENSYM = 11,        // length symbol 286 / 287
-    ERR_GUARD = 12          // more decoding steps than any valid block of this size can take (the loops' own exit conditions
+    ERR_GUARD = 12,         // more decoding steps than any valid block of this size can take (the loops' own exit conditions
                             // make this unreachable; it is the belt to their braces: a wave must always drain)
+    ERR_INCOMPLETE = 13     // a dynamic block's code leaves code space unused (dynamic_tables() says which such codes are allowed)
 };
 
 constexpr int LIT_ROOT = 10;            // bits of the literal/length root table
@@ -296,8 +298,10 @@ struct Chain {
     }
 
     // ---- Huffman tables ----
-    // code lengths cl[0 .. n) -> root table of RB bits, canonical triples, sorted symbols.  false: over-subscribed.
-    XMI_HD bool build(const uint8_t *cl, uint32_t n, uint16_t *root, uint32_t RB, uint16_t *sym, uint16_t (*meta)[16])
+    // code lengths cl[0 .. n) -> root table of RB bits, canonical triples, sorted symbols.  Returns the code space the lengths leave
+    // unused, in units of 2^-15: 0 a complete code, < 0 an over-subscribed one (nothing is built then).  m->cnt[L] is the number of
+    // codes of L bits afterwards.
+    XMI_HD int32_t build(const uint8_t *cl, uint32_t n, uint16_t *root, uint32_t RB, uint16_t *sym, uint16_t (*meta)[16])
     {
         XMI_STAGE(40);
         chain_sync();
@@ -316,7 +320,7 @@ struct Chain {
         for (uint32_t L = 1; L < 16u; ++L) {
             const uint32_t c = m->cnt[L];
             left = (left << 1) - (int32_t)c;
-            if (left < 0) return false;
+            if (left < 0) return left;
             first[L] = code; base[L] = idx;
             if (gl == 0u) { meta[0][L] = (uint16_t)code; meta[1][L] = (uint16_t)(code + c); meta[2][L] = (uint16_t)idx; }
             code = (code + c) << 1;
@@ -355,7 +359,7 @@ struct Chain {
                 }
             }
             chain_sync();
-            return true;
+            return left;
         }
 #endif
         for (uint32_t i = gl; i < 16u; i += GS) m->cnt[i] = 0u;          // now: symbols of each length placed so far
@@ -377,8 +381,11 @@ struct Chain {
             }
             chain_sync();
         }
-        return true;
+        return left;
     }
+    // What zlib accepts of a literal/length or distance code that is not complete, and so what encoders may send: no code at all
+    // (the distance code of a block of literals) and a single code of one bit.  Everything else is damage (left: build()'s result).
+    XMI_HD bool code_allowed(int32_t left) const { return left == 0 || left == 32768 || (left == 16384 && m->cnt[1] == 1u); }
     // one symbol; at least 15 valid bits must be buffered (need32 before)
     XMI_HD uint32_t decode(const uint16_t *root, uint32_t RB, const uint16_t *sym, const uint16_t (*meta)[16])
     {
@@ -422,8 +429,9 @@ struct Chain {
         for (uint32_t s = gl; s < 288u; s += GS) m->cl[s] = (uint8_t)(s < 144u ? 8 : s < 256u ? 9 : s < 280u ? 7 : 8);
         for (uint32_t s = gl; s < 32u; s += GS) m->cl[288u + s] = 5;
         chain_sync();
-        return build(m->cl, 288u, m->lit_root, LIT_ROOT, m->lit_sym, m->lit_meta) &&
-               build(m->cl + 288, 30u, m->dist_root, DIST_ROOT, m->dist_sym, m->dist_meta);
+        // (the distance code is incomplete by the RFC's design: 30 of 32 five-bit codes)
+        return build(m->cl, 288u, m->lit_root, LIT_ROOT, m->lit_sym, m->lit_meta) >= 0 &&
+               build(m->cl + 288, 30u, m->dist_root, DIST_ROOT, m->dist_sym, m->dist_meta) >= 0;
     }
     XMI_HD bool dynamic_tables()
     {
@@ -440,7 +448,10 @@ struct Chain {
             if (gl == 0u) m->cl[320u + at] = (uint8_t)v;
         }
         chain_sync();
-        if (!build(m->cl + 320, 19u, m->dist_root, CLC_ROOT, m->dist_sym, m->dist_meta)) { err = ERR_OVERSUB; return false; }
+        // every code of a dynamic block must use its code space up, as zlib demands (a stream it refuses is a damaged stream here
+        // too): the code-length code always, the other two but for the forms code_allowed() names
+        const int32_t clc_left = build(m->cl + 320, 19u, m->dist_root, CLC_ROOT, m->dist_sym, m->dist_meta);
+        if (clc_left != 0) { err = clc_left < 0 ? ERR_OVERSUB : ERR_INCOMPLETE; return false; }
         XMI_STAGE(50);
         uint32_t i = 0, prev = 0;
         const uint32_t total = hlit + hdist;
@@ -470,8 +481,12 @@ struct Chain {
         }
         chain_sync();
         if (m->cl[256] == 0) { err = ERR_NO_EOB; return false; }
-        if (!build(m->cl, hlit, m->lit_root, LIT_ROOT, m->lit_sym, m->lit_meta) ||
-            !build(m->cl + hlit, hdist, m->dist_root, DIST_ROOT, m->dist_sym, m->dist_meta)) { err = ERR_OVERSUB; return false; }
+        const int32_t lit_left = build(m->cl, hlit, m->lit_root, LIT_ROOT, m->lit_sym, m->lit_meta);
+        if (lit_left < 0) { err = ERR_OVERSUB; return false; }
+        if (!code_allowed(lit_left)) { err = ERR_INCOMPLETE; return false; }
+        const int32_t dist_left = build(m->cl + hlit, hdist, m->dist_root, DIST_ROOT, m->dist_sym, m->dist_meta);
+        if (dist_left < 0) { err = ERR_OVERSUB; return false; }
+        if (!code_allowed(dist_left)) { err = ERR_INCOMPLETE; return false; }
         return true;
     }
     XMI_HD void copy_match(uint32_t len, uint32_t dist)
