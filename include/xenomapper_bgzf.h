@@ -177,7 +177,9 @@ typedef struct {
     int64_t  mismatch_at;            /* first pair whose names differ (AssertionError, :106) or -1                               */
     int32_t  bad_block;              /* != 0: a BGZF block failed (decoder status or CRC-32), a malformed record, or a file that
                                         ends inside a record: nothing else is meaningful                                         */
-    int32_t  unaligned;              /* 1: a block does not begin with a record: no record table, use the host decoder           */
+    int32_t  unaligned;              /* 1: a block does not begin with a record (or holds more record starts than alignment
+                                        records can have, the window's last block included): no record table, use the host
+                                        decoder                                                                                  */
     int32_t  weird;                  /* 1: a record the text rules might read differently: use the host decoder for this window  */
     int32_t  reserved;
     uint64_t n_exceptions;           /* pairs whose flags carry XMS_LINE_EX_A / _EX_X on either record                           */

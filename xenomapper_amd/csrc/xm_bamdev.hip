@@ -124,8 +124,11 @@ scan_kernel(const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ exit_
     for (uint32_t s = a; s < b; ++s) {
         sum += cnt[s];
         // the chain of segment s must land exactly on the first byte of segment s + 1; the last one may stop anywhere
-        // (an incomplete record at the end of the window) but must not have been cut short by a later segment's start
-        if (s + 1 < n_seg && exit_at[s] != seg_start[s + 1]) misaligned = 1;
+        // (an incomplete record at the end of the window) but must not have been cut short by a later segment's start.  An exit
+        // of 0xFFFFFFFF (the inflate launch: more record starts than the block's slots hold, or a block that did not inflate)
+        // means that segment's slots were not filled, the last one's too: never a window the record kernels may read
+        const uint32_t e = exit_at[s];
+        if (e == 0xFFFFFFFFu || (s + 1 < n_seg && e != seg_start[s + 1])) misaligned = 1;
     }
     part[t] = sum;
     if (misaligned) atomicOr(&bad, 1u);
@@ -1701,7 +1704,7 @@ int xm_bamdev_run(xm_bamdev *b, int slot, const xm_bamdev_input in[2], int score
     if (out->mismatch_at < 0) {
         for (int f = 0; f < 2 && !open_run; ++f) {
             const bool exhausted = n == n_can[f];                           // the window holds no further complete record (or run)
-            if (exhausted && whole[f]) ended = true;
+            if (exhausted && whole[f] && n < max_records) ended = true;     // (a walk that stopped at max_records has not looked: xmh_parse)
         }
         if (!ended && n < max_records) starved = true;                      // a window ran out before the other file did
     }
