@@ -380,7 +380,9 @@ int xm_classify_runs_f64_dev(xm_ctx *ctx, void *stream, int mode, uint64_t n_rec
                              uint16_t *runs16, uint16_t *gran_counts, uint64_t *n_out, uint64_t *counts);
 
 /* Host memory, no device: list `bin` (0..6) of the segmented form as a flat list of record indices in input order;
- * *n_written = its length (entries past `capacity` are counted, not stored; idx_out may be NULL to count only). */
+ * *n_written = its length (entries past `capacity` are counted, not stored; idx_out may be NULL to count only).
+ * XM_ERR_INVALID_ARG for a bin outside 0..6, n_written NULL, and counts of a granule that sum past 2048 (whichever bin is
+ * asked for: such counts are not the kernel's); *n_written is then left as it was. */
 int xm_runs_expand(uint64_t n_records, const uint16_t *runs16, const uint16_t *gran_counts, int bin,
                    uint32_t *idx_out, uint64_t capacity, uint64_t *n_written);
 

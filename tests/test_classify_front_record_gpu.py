@@ -66,7 +66,10 @@ def oracle(mode, cols, bits, m):
     return want_code, want_counts, want_idx, want_off, want_bins
 
 
-def check_flat(ctx, mode, cols, bits, m, want):
+ALL_FORMS = ((False, True), (True, False), (True, True))           # (category bytes, compact stream bins4)
+
+
+def check_flat(ctx, mode, cols, bits, m, want, forms=ALL_FORMS):
     """xm_classify_compact*_dev with the compact stream only, the category bytes only, and both, against the oracle."""
     import torch
     from xenomapper_amd import _ffi
@@ -75,7 +78,7 @@ def check_flat(ctx, mode, cols, bits, m, want):
     n = cols[0].shape[0]
     d = [torch.from_numpy(np.ascontiguousarray(c)).to(dev) for c in cols]
     dbits = torch.from_numpy(np.ascontiguousarray(bits).view(np.int64)).to(dev)
-    for with_code, with_bins4 in ((False, True), (True, False), (True, True)):
+    for with_code, with_bins4 in forms:
         code = torch.full((n + 16,), 0xEE, dtype=torch.uint8, device=dev) if with_code else None
         bins4 = torch.full((_ffi.bins4_bytes(n),), 0xEE, dtype=torch.uint8, device=dev) if with_bins4 else None
         idx = torch.full((n,), -1, dtype=torch.int32, device=dev)

@@ -2,7 +2,9 @@
 the runs must give exactly the oracle's stable split (oracle/xm_oracle.c: xmo_classify_* + xmo_compact, restating
 xenomapper.py:321-350, :398-452, :498-554), at every size of the flat forms' parity test, at BASELINE.json's full
 sizes, single-end, binary64 with NaN, and irregular unit masks.  Two expansions are checked against each other too: the
-C ABI's xm_runs_expand and an independent NumPy one written from the header's description of the layout."""
+C ABI's xm_runs_expand and an independent NumPy one written from the header's description of the layout (np_expand of
+tests/runs_shapes.py).  Every call that check_runs makes is also held to the header's write contract: nothing stored past a
+granule's units, count 7 of a granule 0, nothing touched behind the last granule (guard entries behind both arrays)."""
 import itertools
 
 import numpy as np
@@ -10,6 +12,7 @@ import pytest
 
 from tests import helpers as H
 from tests.helpers import NEG
+from tests.runs_shapes import np_expand
 
 pytestmark = pytest.mark.gpu
 
@@ -25,24 +28,13 @@ def ctx():
     c.close()
 
 
-def np_expand(n, runs16, gran_counts, b):
-    """List b from the layout as include/xenomapper_hip.h describes it (NumPy, no library call)."""
-    n_gran = (n + GRAN - 1) // GRAN
-    c = gran_counts[:8 * n_gran].reshape(n_gran, 8).astype(np.int64)
-    start = np.cumsum(c, axis=1) - c                              # where bin b begins inside the granule's slab
-    k = c[:, b]
-    total = int(k.sum())
-    if total == 0:
-        return np.zeros(0, dtype=np.uint32)
-    g = np.repeat(np.arange(n_gran, dtype=np.int64), k)           # granule of every unit of the list
-    first = np.cumsum(k) - k
-    within = np.arange(total, dtype=np.int64) - np.repeat(first, k)
-    at = g * GRAN + np.repeat(start[:, b], k) + within
-    return (g * GRAN + runs16[at].astype(np.int64)).astype(np.uint32)
+GUARD = 64                              # entries behind runs16 and gran_counts that a call must leave alone
+PREFILL = 0xA5C3                        # no record number (0..2047), and not what an idle LDS slab is likely to hold
 
 
 def run_runs(ctx, mode, cols, bits, m):
-    """-> host (runs16, gran_counts, n_out, counts) of one xm_classify_runs*_dev call."""
+    """-> host (runs16, gran_counts, n_out, counts) of one xm_classify_runs*_dev call; both arrays with their GUARD entries,
+    everything the call did not write still PREFILL."""
     import torch
     from xenomapper_amd import _ffi
     dev = torch.device("cuda:0")
@@ -50,14 +42,31 @@ def run_runs(ctx, mode, cols, bits, m):
     n_gran = max(_ffi.runs_granules(n), 1)
     d = [torch.from_numpy(np.ascontiguousarray(c)).to(dev) for c in cols]
     dbits = torch.from_numpy(np.ascontiguousarray(bits).view(np.int64)).to(dev)
-    runs = torch.full((n_gran * GRAN,), -1, dtype=torch.int16, device=dev)
-    gcnt = torch.full((n_gran * 8,), -1, dtype=torch.int16, device=dev)
+    fill = int(np.array(PREFILL, dtype=np.uint16).view(np.int16))
+    runs = torch.full((n_gran * GRAN + GUARD,), fill, dtype=torch.int16, device=dev)
+    gcnt = torch.full((n_gran * 8 + GUARD,), fill, dtype=torch.int16, device=dev)
     n_out = torch.full((8,), -1, dtype=torch.int64, device=dev)
     counts = torch.full((64,), -1, dtype=torch.int64, device=dev)
     ctx.classify_runs_dev(mode, *d, dbits, m, runs, gcnt, n_out, counts)
     torch.cuda.synchronize()
     return (runs.cpu().numpy().view(np.uint16), gcnt.cpu().numpy().view(np.uint16),
             n_out.cpu().numpy().astype(np.uint64), counts.cpu().numpy().astype(np.uint64))
+
+
+def check_write_contract(n, runs16, gcnt, want_idx):
+    """include/xenomapper_hip.h: entries of runs16 past a granule's units (the oracle's) are not written; count 7 of a granule
+    is 0; and nothing behind the last granule is touched, in either array."""
+    from xenomapper_amd import _ffi
+    n_gran = _ffi.runs_granules(n)
+    assert (runs16[n_gran * GRAN:] == PREFILL).all() and (gcnt[n_gran * 8:] == PREFILL).all()
+    if n_gran == 0:
+        return
+    assert (gcnt[:8 * n_gran].reshape(n_gran, 8)[:, 7] == 0).all()
+    units = np.bincount(want_idx.astype(np.int64) // GRAN, minlength=n_gran)
+    behind = np.arange(GRAN)[None, :] >= units[:, None]
+    touched = behind & (runs16[:n_gran * GRAN].reshape(n_gran, GRAN) != PREFILL)
+    assert not touched.any(), ("written past the granule's units: (granule, entry, units of the granule)",
+                               [(int(a), int(b), int(units[a])) for a, b in np.argwhere(touched)[:8]])
 
 
 def check_runs(ctx, mode, cols, bits, m, want=None):
@@ -74,6 +83,7 @@ def check_runs(ctx, mode, cols, bits, m, want=None):
         assert int(n_out[b]) == int(want_off[b + 1] - want_off[b]), (b, n_out, want_off)
     assert int(n_out[7]) == int(want_off[7])
     if n == 0:
+        check_write_contract(n, runs16, gcnt, want_idx)
         return
     n_gran = _ffi.runs_granules(n)
     g = gcnt[:8 * n_gran].reshape(n_gran, 8)
@@ -83,6 +93,7 @@ def check_runs(ctx, mode, cols, bits, m, want=None):
         got = np_expand(n, runs16, gcnt, b)
         assert np.array_equal(got, want_list), (mode, b)
         assert np.array_equal(_ffi.runs_expand(n, runs16, gcnt, b), want_list), (mode, b)
+    check_write_contract(n, runs16, gcnt, want_idx)
     assert ctx.workspace_is_clean()
 
 

@@ -672,7 +672,8 @@ class Context(object):
     def classify_runs_dev(self, mode, as1, xs1, as2, xs2, unit_bits, min_score, runs16, gran_counts, n_out, counts, stream=None):
         """The fused main loop with SEGMENTED bin lists, one launch (xm_classify_runs*_dev): runs16 = int16 device tensor of
         runs_granules(n) * 2048 entries, gran_counts = int16 device tensor of runs_granules(n) * 8, n_out 8 x int64,
-        counts 64 x int64.  Columns int32 or float64.  Asynchronous."""
+        counts 64 x int64.  Columns int32 or float64.  Entries of runs16 past a granule's units are not written.
+        Asynchronous."""
         n = as1.numel()
         st = self._stream_handle(stream)
         ptrs = [ctypes.c_void_p(t.data_ptr()) for t in (as1, xs1, as2, xs2, unit_bits)]

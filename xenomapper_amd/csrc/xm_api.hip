@@ -776,10 +776,11 @@ int xm_runs_expand(uint64_t n, const uint16_t *runs16, const uint16_t *gran_coun
     uint64_t w = 0;
     for (uint64_t g = 0; g < n_gran; ++g) {
         const uint16_t *c = gran_counts + g * 8;
-        uint32_t at = 0;
+        uint32_t at = 0, all = 0;
         for (int b = 0; b < bin; ++b) at += c[b];
+        for (int b = 0; b < 8; ++b) all += c[b];
         const uint32_t k = c[bin];
-        if (at + k > XM_GRAN) return XM_ERR_INVALID_ARG;                  // not counts the kernel wrote
+        if (all > XM_GRAN) return XM_ERR_INVALID_ARG;                     // not counts the kernel wrote, whichever bin is asked for
         const uint16_t *run = runs16 + g * XM_GRAN + at;
         for (uint32_t i = 0; i < k; ++i, ++w)
             if (idx_out && w < capacity) idx_out[w] = (uint32_t)(g * XM_GRAN) + run[i];

@@ -1058,9 +1058,19 @@ __device__ __forceinline__ void classify_runs_body(const T *__restrict__ as1, co
         if (bin[j] < 7u) slab[at + pos[j]] = (uint16_t)(threadIdx.x * 4u + (uint32_t)j);
     }
     __syncthreads();                                                     // the slab and the histogram are complete
-    // the slab as it stands: 16 bytes per thread (entries past the granule's units are not written)
-    if (threadIdx.x < (uint32_t)(XM_GRAN / 8) && threadIdx.x * 8u < units)
-        reinterpret_cast<uint4 *>(rs.runs16 + (uint64_t)g * XM_GRAN)[threadIdx.x] = reinterpret_cast<const uint4 *>(slab)[threadIdx.x];
+    // the slab as it stands: 16 bytes per thread; the one thread whose group holds the granule's last unit stores its
+    // valid entries one by one (the slab behind them was never written: entries past the granule's units are not written)
+    {
+        uint16_t *out = rs.runs16 + (uint64_t)g * XM_GRAN;
+        const uint32_t e0 = threadIdx.x * 8u;
+        if (e0 + 8u <= units) {
+            reinterpret_cast<uint4 *>(out)[threadIdx.x] = reinterpret_cast<const uint4 *>(slab)[threadIdx.x];
+        } else if (e0 < units) {
+#pragma unroll
+            for (uint32_t e = 0; e < 7u; ++e)
+                if (e0 + e < units) out[e0 + e] = slab[e0 + e];
+        }
+    }
     if (wave == 0u) {
         if (lane < 8u) rs.gran_counts16[(uint64_t)g * 8u + lane] = (uint16_t)tot;
         const uint4 h0 = *reinterpret_cast<const uint4 *>(lds + lane * XM_HREP);
