@@ -499,3 +499,106 @@ def test_gpu_bam_cursor_reads_the_reference_names(tmp_path):
             assert g.ref_names == want
         finally:
             g.close()
+
+
+MIB = 1 << 20
+
+
+@pytest.mark.parametrize("args, want, grow, raw_cap", [
+    # (wanted bytes, windows so far, largest carried tail, most bytes a file has left, worst case) -> bytes staged, grow, raw_cap
+    # a full window of 512 MiB and plenty of input: a quarter, a half, then full windows; the short ones are followed by a full
+    # one in the same slot, so every slot is sized for that: 512 + 512 / 16 + 1 MiB
+    ((512 * MIB, 0, 0, 10240 * MIB, False), 128 * MIB, 2.0, 545 * MIB),
+    ((512 * MIB, 1, 0, 10240 * MIB, False), 256 * MIB, 2.0, 545 * MIB),
+    ((512 * MIB, 2, 0, 10240 * MIB, False), 512 * MIB, 1.0, 545 * MIB),
+    ((512 * MIB, 7, 0, 10240 * MIB, False), 512 * MIB, 1.0, 545 * MIB),
+    # a file that ends before a full window comes: the quarter window's own size, 128 + 32 + 1
+    ((512 * MIB, 0, 0, 100 * MIB, False), 128 * MIB, 2.0, 161 * MIB),
+    # twice what is left is exactly a full window: sized for the full one; one byte less: not
+    ((512 * MIB, 0, 0, 256 * MIB, False), 128 * MIB, 2.0, 545 * MIB),
+    ((512 * MIB, 1, 0, 256 * MIB - 1, False), 256 * MIB, 2.0, 289 * MIB),
+    # nothing shrinks below 64 MiB
+    ((64 * MIB - 1, 0, 0, 10240 * MIB, False), 64 * MIB - 1, 1.0, 64 * MIB - 1 + (64 * MIB - 1) // 16 + MIB),
+    ((64 * MIB, 0, 0, 0, False), 16 * MIB, 2.0, 21 * MIB),
+    ((64 * MIB, 0, 0, 10240 * MIB, False), 16 * MIB, 2.0, 69 * MIB),
+    # a carried tail longer than a sixteenth of the window takes its own room, in short windows and full ones
+    ((64 * MIB, 2, 10 * MIB, 10240 * MIB, False), 64 * MIB, 1.0, 75 * MIB),
+    ((64 * MIB, 2, 4 * MIB + 1, 10240 * MIB, False), 64 * MIB, 1.0, 69 * MIB + 1),
+    ((64 * MIB, 1, 10 * MIB, 0, False), 32 * MIB, 2.0, 43 * MIB),
+    ((64 * MIB, 1, 10 * MIB, 10240 * MIB, False), 32 * MIB, 2.0, 75 * MIB),
+    # the worst-case flag changes the staging alone
+    ((512 * MIB, 2, 0, 10240 * MIB, True), 512 * MIB, 1.0, 545 * MIB),
+    ((64 * MIB, 0, 0, 0, True), 16 * MIB, 2.0, 21 * MIB),
+])
+def test_bam_window_sizes(args, want, grow, raw_cap):
+    """_bam_window_sizes, the sizes of one window of the GPU BAM path: quarter, half, then full windows (none below 64 MiB), the
+    slot sized for the window plus the larger of the carried tail and a sixteenth of the full window plus 1 MiB -- for the full
+    window where one will follow in the slot --, staging for half of that plus 64 KiB (all of it in the worst case), a block per
+    64 KiB and per 4 KiB plus 64, and a record per 36 bytes plus 2, capped at FILE_MAX_RECORDS."""
+    from xenomapper_amd import xenomapper as xm
+    got = xm._bam_window_sizes(*args)
+    assert (got.want, got.grow, got.raw_cap) == (want, grow, raw_cap)
+    assert got.comp_cap == (raw_cap if args[4] else raw_cap // 2 + 65536)
+    assert got.max_blocks == raw_cap // 65536 + raw_cap // 4096 + 64
+    assert xm.FILE_MAX_RECORDS == 1 << 22
+    assert got.max_records == min(1 << 22, raw_cap // 36 + 2)
+    assert (got.max_records == 1 << 22) == (raw_cap >= 144 * MIB - 72)       # (2^22 - 2 records of 36 bytes: both sides occur)
+
+
+def test_the_helper_threads_reserve_of_the_other_slot_ends_before_the_next_window_reserves_it(monkeypatch):
+    """The run's first BAM window has the helper thread reserve the OTHER slot.  When both files reach their end in that window
+    no read-ahead follows it, and the next window's own reserve of that slot must still wait for it: two reserves of one slot
+    never overlap.  Stand-ins: a front end whose reserve sleeps, sources that stage nothing and report the end."""
+    import time
+    import types
+    import numpy as np
+    from xenomapper_amd import _ffi, xenomapper as xm
+
+    class FrontEnd(object):
+        ctx, _h, spans = object(), True, []
+
+        def reserve(self, slot, *caps):
+            start = time.perf_counter()
+            time.sleep(0.05)
+            self.spans.append((slot, start, time.perf_counter()))
+
+        def run(self, slot, inputs, *args, **kw):
+            return types.SimpleNamespace(slot=slot, n=0, n_exceptions=0, bad_block=0, unaligned=False, weird=False, ended=False,
+                                         raw_len=(0, 0), consumed=(0, 0), ms_inflate=0.0, ms_kernels=0.0)
+
+        def fetch_raw(self, slot, blk):
+            pass
+
+    class Source(object):
+        ref_names = ahead = None
+        carry, bytes_per_record, cursor, at_end, ahead_hits, ahead_misses = (0, 0, 0), 0.0, 0, False, 0, 0
+        data = np.zeros(1024, dtype=np.uint8)
+
+        def __init__(self, path, n_threads):
+            pass
+
+        def stage(self, *args):
+            return {"eof": True, "carry_len": 0, "skip": 0}
+
+        def ran(self, *args, **kw):
+            pass
+
+        def close(self):
+            pass
+
+    dev = FrontEnd()
+    for name in ("XENOMAPPER_GPU_BAM", "XENOMAPPER_BAM_READ_AHEAD"):
+        monkeypatch.delenv(name, raising=False)
+    monkeypatch.setattr(xm, "_context", dev.ctx)
+    monkeypatch.setattr(xm, "_bamdev", dev)
+    monkeypatch.setattr(xm, "_GpuBamFile", Source)
+    run = xm._FileRun(_ffi.MODE_PE_LIBERAL, "1.bam", "2.bam", [None] * 6, float("-inf"), xm.get_tag, False, 2, bam=True)
+    try:
+        for which in (0, 1):
+            win = run.parse_next(which, MIB)
+            assert win.eofs == [True, True] and not win.block.ended
+    finally:
+        run.close()
+    assert sorted(slot for slot, _start, _end in dev.spans) == [0, 1, 1]         # the helper's reserve of slot 1, then the window's
+    (_, _, first_end), (_, second_start, _) = sorted(span for span in dev.spans if span[0] == 1)
+    assert second_start >= first_end

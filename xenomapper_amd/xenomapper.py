@@ -35,7 +35,7 @@ import struct
 import sys
 import threading
 import time
-from collections import Counter
+from collections import Counter, namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -1250,7 +1250,11 @@ class _PhaseClock(dict):
         try:
             yield
         finally:
-            self[name] = self.get(name, 0.0) + time.perf_counter() - start
+            self.add(name, time.perf_counter() - start)
+
+    def add(self, key, value):
+        """Add `value` to counter `key`: a count stays an int, seconds and milliseconds a float."""
+        self[key] = self.get(key, 0) + value
 
 
 def _quietly(fn, *args):
@@ -1610,521 +1614,220 @@ class _GpuBamFile(object):
         self.reader.close()
 
 
-def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_threads=0, bam=False, starts=None, out_bam=False,
-               bam_compress=False):
-    """The three main loops on two SAM (or BAM) *files*: same results as _run(mode, getReadPairs(...)), with the
-    text work done by the C++ stripper / writer.  Falls back to the Python reader when the input is not ASCII.
-    out_bam: the sinks (_BamSink, one per bin) get the units' alignment records as BGZF members instead of their SAM text -- the
-    windows the device takes gathered and framed there (xm_bamdev_fetch_bins_bam; bam_compress: gathered, deflated and framed there,
-    xm_bamdev_fetch_bins_bamz), the others assembled by _bam_records_of."""
-    from . import _host
-    ctx = default_context()
-    paired = mode != _ffi.MODE_SE
-    cigar_mode = tag_func is get_cigarbased_AS_tag
-    score_mode = _host.SCORE_CIGAR if cigar_mode else (_host.SCORE_AS_ZS if tag_func is get_tag_with_ZS_as_XS
-                                                       else _host.SCORE_AS_XS)
-    if not n_threads:                                                # 0: the CPUs this process may use (cgroup-aware)
-        n_threads = int(os.environ.get("XENOMAPPER_THREADS", "0"))
-    prof = _PhaseClock()
-    _EMIT_CLOCK.clear()
-    t_all = time.perf_counter()
-    # BAM on the GPU (include/xenomapper_bgzf.h): inflate + record chain + stripper on the device, either walk, the three plugins
-    # (--cigar_scores: NM and the records' CIGAR words become the packed CIGAR columns on the device); XENOMAPPER_GPU_BAM=0 keeps
-    # the host decoder
-    bamdev = None
-    if (bam and min_score == min_score and os.environ.get("XENOMAPPER_GPU_BAM", "1") != "0"):
-        try:
-            bamdev = default_bamdev()
-        except MemoryError:
-            bamdev = None
-    if out_bam and bamdev is None:
-        raise RuntimeError("BAM outputs need the GPU BAM front end (BAM inputs, a min_score that is a number, XENOMAPPER_GPU_BAM "
-                           "not 0, and memory for its buffers)")
-    with prof("open"):
-        if bamdev is not None:
-            sources = [_GpuBamFile(path, n_threads) for path in (path1, path2)]
-        else:
-            sources = [(_BamSource(path, n_threads) if bam else _SamSource(path, None if starts is None else starts[k]))
-                       for k, path in enumerate((path1, path2))]
-        # Two parsers alternate so that the next window is decoded (BAM) and parsed in a helper thread -- the C++
-        # code runs without the GIL -- while the GPU classifies and the writer emits the current one.
-        parsers = [_host.Parser(n_threads), _host.Parser(n_threads)]
-        pool = ThreadPoolExecutor(max_workers=1)
-        # output files extended ahead of the writer, their pages unmapped behind it (more helper threads than two measured no
-        # better: profiles/r06_ab_sam_bins.txt)
-        ahead, ahead_pool = {}, ThreadPoolExecutor(max_workers=max(1, int(os.environ.get("XENOMAPPER_AHEAD_THREADS", "2"))))
-    totals, key_order = Counter(), []
-    window = FILE_WINDOW_BYTES
-    active = [s for s in sinks if s]
-    distinct = len(set(id(s) for s in active)) == len(active)
-    # SAM text: the text itself goes to the GPU and is split there (include/xenomapper_strip.h) -- the host threads only copy
-    # windows into page-locked memory and write the outputs.  XENOMAPPER_GPU_STRIP=0 keeps the host stripper.
-    stripper = None
-    if not bam and min_score == min_score and os.environ.get("XENOMAPPER_GPU_STRIP", "1") != "0":
-        try:
-            stripper = default_stripper()
-        except MemoryError:                                          # no room for its buffers: the host threads strip
-            stripper = None
+def _ordered_counts(totals, key_order):
+    """The counters of a run in the order in which their keys first came up."""
+    ordered = Counter()
+    for key in key_order:
+        ordered[key] = totals[key]
+    return ordered
 
-    # SAM text: the outputs gathered on the device as well (every bin needs a sink of its own; XENOMAPPER_GPU_SAM_BINS=0: the host gathers)
-    sam_bins_on_device = stripper is not None and distinct and os.environ.get("XENOMAPPER_GPU_SAM_BINS", "1") != "0"
-    bam_text = _BAM_TEXT_BUFFERS                                     # (slot, file) -> [text bytes, line_off, line_len] of the GPU BAM path
-    bam_windows = [0]                                                # windows run so far
-    # the records' SAM text is printed on the device when the reference names could be read (XENOMAPPER_GPU_BAM_TEXT=0: by the
-    # host threads, from the packed records; a window with floating-point fields is printed that way in any case)
-    bam_text_on_device = [False]
-    ref_shift = 0                                                    # BAM outputs: file 2's reference ids in `unresolved` (its list follows file 1's)
-    if out_bam and sinks[4]:
-        if sources[0].ref_names is None:
-            raise ValueError("the reference list of %s could not be read: `unresolved` cannot be written as BAM" % path1)
-        ref_shift = len(sources[0].ref_names)
-    if bamdev is not None and not out_bam and os.environ.get("XENOMAPPER_GPU_BAM_TEXT", "1") != "0" and all(src.ref_names is not None for src in sources):
-        for f, src in enumerate(sources):
-            bamdev.set_refs(f, src.ref_names)
-        bam_text_on_device[0] = True
-    # ... and gathered there into the six outputs (xm_bamdev_fetch_bins: the host writes six byte ranges per window instead of
-    # gathering the lines; needs every bin to have a sink of its own -- two bins sharing one are written unit by unit, _emit_shared).
-    # XENOMAPPER_GPU_BAM_BINS=0: the device prints, the host gathers (round 5's form)
-    bam_bins_on_device = [bam_text_on_device[0] and distinct and os.environ.get("XENOMAPPER_GPU_BAM_BINS", "1") != "0"]
-    # BAM outputs: records gathered and framed on the device (xm_bamdev_fetch_bins_bam; XENOMAPPER_GPU_BAM_BINS=0: the packed records
-    # come back and the host assembles)
-    bam_out_on_device = out_bam and os.environ.get("XENOMAPPER_GPU_BAM_BINS", "1") != "0"
-    # the GPU BAM path reads the next window's compressed blocks while the GPU works on the current one (_GpuBamFile.read_ahead):
-    # a reader of its own (8 threads: pread into page-locked memory peaks there, e2e.host_ceilings) and one thread that drives it
-    bam_reader = _host.Parser(8) if bamdev is not None and os.environ.get("XENOMAPPER_BAM_READ_AHEAD", "1") != "0" else None
-    bam_ahead_pool = ThreadPoolExecutor(max_workers=1) if bam_reader is not None else None
-    bam_ahead = [None]                                               # the read-ahead in flight
-    bam_comp_worst_case = [False]                                    # a window's compressed bytes outgrew the staging reserved for half the inflated size
 
-    def print_records(which, f, raw_addr, rec_off_addr, n, sparse=False, wanted=None):
-        """SAM text of records [0, n) of a window decoded on the GPU -> (text array, line_off, line_len)."""
-        buf = bam_text.get((which, f))
-        if buf is None or buf[1].shape[0] < n:
-            text = buf[0] if buf is not None else np.empty(1 << 20, dtype=np.uint8)
-            buf = bam_text[(which, f)] = [text, np.empty(n + n // 4 + 64, dtype=np.uint32), np.empty(n + n // 4 + 64, dtype=np.uint32)]
-        while True:
-            got = sources[f].reader.print_records(raw_addr, rec_off_addr, n, buf[0], buf[1], buf[2], sparse, wanted)
-            if got >= 0:
-                return buf[0], buf[1], buf[2], got
-            buf[0] = np.empty(-got + (-got >> 3) + (1 << 16), dtype=np.uint8)
+_BamWindowSizes = namedtuple("_BamWindowSizes", "want grow raw_cap comp_cap max_blocks max_records")
 
-    def parse_next_bamdev(which, want):
-        """One window of both BAM files on the GPU: stage compressed blocks, xm_bamdev_run (inflate, CRC, record chain, strip,
-        pair), print the records' text for the writer.  A window the device does not vouch for -- blocks that do not begin
-        with a record, a record the text rules might read differently -- is printed whole and stripped by the text rules."""
+
+def _bam_window_sizes(want, windows_so_far, carried, most_left, worst_case):
+    """What one window of the GPU BAM path asks for, from numbers alone.  want: inflated bytes of a full window; windows_so_far:
+    windows this run has started; carried: the largest tail a file carries into this window; most_left: the most compressed bytes
+    any file still has; worst_case: a window's compressed bytes have outgrown the staging reserved for half the inflated size.
+    -> want (inflated bytes to stage per file), grow (the window behind this one over this one, for the read-ahead), the slot's
+    capacities raw_cap / comp_cap / max_blocks, and max_records."""
+    # the first windows are small: nothing can be printed or written before the first window is through the GPU, so the
+    # pipeline is filled with a quarter and a half window before the full ones (which use the chip best) follow
+    grow = 1.0
+    full = want
+    if windows_so_far < 2 and want >= (64 << 20):
+        want = want >> (2 - windows_so_far)
+        grow = 2.0
+    # (room for a tail of a sixteenth of the window: a tail a little longer than the last one is no reason to make every buffer again)
+    carried = max(carried, full // 16)
+    raw_cap = want + carried + (1 << 20)
+    if want < full and most_left * 2 >= full:
+        # a full window will follow in this slot: its buffers are made once, for that, not for the quarter and again
+        # for the whole (page-locking is the first run's largest cost: 0.50 s of 0.80 on 4.5 GB of BAM)
+        raw_cap = full + carried + (1 << 20)
+    # DEFLATE never expands a block by more than a few bytes; BAM as the aligners and samtools write it is a third of its
+    # inflated size, so the page-locked staging is reserved for half and grows (once per process) for input that is not
+    comp_cap = raw_cap if worst_case else raw_cap // 2 + (64 << 10)
+    max_blocks = raw_cap // 65536 + raw_cap // 4096 + 64
+    # (no alignment record is shorter than 36 bytes)
+    return _BamWindowSizes(want, grow, raw_cap, comp_cap, max_blocks, min(FILE_MAX_RECORDS, raw_cap // 36 + 2))
+
+
+class _Window(object):
+    """What parse_next hands to settle for one window of both inputs.  block: the parsed or stripped block; raws, pos: per file,
+    the text the block's line tables point into and the offset they count from; eofs: per file, whether the window reached the
+    end.  The rest is there only for windows a device front end took further: classified = (code, idx, bin_offsets, counts) of a
+    fused pass that ran right behind the strip kernels; bins = the six outputs gathered on the device (status, bytes, bin
+    offsets); lines = the wanted records' text printed on the device (status, texts, line_off, line_len); packed = the wanted
+    records, packed (addresses, places, bytes); bam_src = (inflated bytes, record offsets) per file for the host's BAM
+    assembler; finish = what settle calls first, with the window, in the main thread."""
+    __slots__ = ("block", "raws", "pos", "eofs", "classified", "bins", "lines", "packed", "bam_src", "finish")
+
+    def __init__(self, block, raws, pos, eofs):
+        self.block, self.raws, self.pos, self.eofs = block, raws, pos, eofs
+        self.classified = self.bins = self.lines = self.packed = self.bam_src = self.finish = None
+
+
+class _FileRun(object):
+    """One file-to-file run (_run_files): its inputs, helper threads and device front end, the switches read from the
+    environment, and the steps of the window loop.  parse_next makes a _Window (in the helper thread, for the window behind the
+    one being written), settle classifies and writes one, close gives everything back."""
+
+    def __init__(self, mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_threads=0, bam=False, starts=None,
+                 out_bam=False, bam_compress=False):
         from . import _host
-        want = max(want, BAM_GPU_WINDOW_BYTES)
-        # the first windows are small: nothing can be printed or written before the first window is through the GPU, so the
-        # pipeline is filled with a quarter and a half window before the full ones (which use the chip best) follow
-        grow = 1.0                                                   # the window behind this one over this one, for the read-ahead
-        full = want
-        if bam_windows[0] < 2 and want >= (64 << 20):
-            want = want >> (2 - bam_windows[0])
-            grow = 2.0
-        bam_windows[0] += 1
-        with prof("window"):
-            if bam_ahead[0] is not None:                             # the read-ahead into this slot's staging buffers has ended
-                try:
-                    bam_ahead[0].result()
-                except Exception:                                    # noqa: BLE001 -- a failed read or copy ahead: stage() does it all
-                    for src in sources:
-                        src.ahead = None
-                bam_ahead[0] = None
-            carried = max(src.carry[2] for src in sources)
-            # (room for a tail of a sixteenth of the window: a tail a little longer than the last one is no reason to make every buffer again)
-            carried = max(carried, full // 16)
-            raw_cap = want + carried + (1 << 20)
-            if want < full and max(src.data.shape[0] - src.cursor for src in sources) * 2 >= full:
-                # a full window will follow in this slot: its buffers are made once, for that, not for the quarter and again
-                # for the whole (page-locking is the first run's largest cost: 0.50 s of 0.80 on 4.5 GB of BAM)
-                raw_cap = full + carried + (1 << 20)
-            # DEFLATE never expands a block by more than a few bytes; BAM as the aligners and samtools write it is a third of its
-            # inflated size, so the page-locked staging is reserved for half and grows (once per process) for input that is not
-            comp_cap = raw_cap if bam_comp_worst_case[0] else raw_cap // 2 + (64 << 10)
-            max_blocks = raw_cap // 65536 + raw_cap // 4096 + 64
-            bamdev.reserve(which, comp_cap, raw_cap, max_blocks, min(FILE_MAX_RECORDS, raw_cap // 36 + 2))
-            if bam_windows[0] == 1 and bam_ahead_pool is not None and not all(src.at_end for src in sources):
-                # the run's first window: the OTHER slot's buffers are made now, by the helper thread, beside this window's work
-                # (page-locking them is a quarter of a process's first run; the read-ahead behind this window then has where to read to)
-                bam_ahead_pool.submit(_quietly, bamdev.reserve, which ^ 1, comp_cap, raw_cap, max_blocks,
-                                      min(FILE_MAX_RECORDS, raw_cap // 36 + 2))
-            # the two files hold the same reads at different bytes per record: each gets a window in proportion, so that the
-            # windows hold about as many records and neither file drags a growing tail from window to window
-            per_rec = [src.bytes_per_record for src in sources]
-            scale = [p / max(per_rec) for p in per_rec] if min(per_rec) > 0 else [1.0, 1.0]
+        self.mode, self.paths, self.sinks, self.min_score, self.tag_func = mode, (path1, path2), sinks, min_score, tag_func
+        self.skip_repeated, self.bam, self.out_bam, self.bam_compress = skip_repeated, bam, out_bam, bam_compress
+        self.ctx = default_context()
+        self.paired = mode != _ffi.MODE_SE
+        self.cigar_mode = tag_func is get_cigarbased_AS_tag
+        self.score_mode = _host.SCORE_CIGAR if self.cigar_mode else (_host.SCORE_AS_ZS if tag_func is get_tag_with_ZS_as_XS
+                                                                     else _host.SCORE_AS_XS)
+        if not n_threads:                                            # 0: the CPUs this process may use (cgroup-aware)
+            n_threads = int(os.environ.get("XENOMAPPER_THREADS", "0"))
+        self.prof = _PhaseClock()
+        _EMIT_CLOCK.clear()
+        self.t_all = time.perf_counter()
+        # BAM on the GPU (include/xenomapper_bgzf.h): inflate + record chain + stripper on the device, either walk, the three plugins
+        # (--cigar_scores: NM and the records' CIGAR words become the packed CIGAR columns on the device); XENOMAPPER_GPU_BAM=0 keeps
+        # the host decoder
+        self.bamdev = None
+        if (bam and min_score == min_score and os.environ.get("XENOMAPPER_GPU_BAM", "1") != "0"):
             try:
-                inputs = [src.stage(bamdev, which, f, parsers[which], int(want * scale[f]) + src.carry[2], max_blocks)
-                          for f, src in enumerate(sources)]
-            except _CompressedBytesOutgrowStaging:
-                bam_comp_worst_case[0] = True
-                prof["bam_staging_regrown"] = prof.get("bam_staging_regrown", 0) + 1
-                bamdev.reserve(which, raw_cap, raw_cap, max_blocks, min(FILE_MAX_RECORDS, raw_cap // 36 + 2))
-                for src in sources:
-                    src.ahead = None                                 # (read into the buffers that were just replaced)
-                inputs = [src.stage(bamdev, which, f, parsers[which], int(want * scale[f]) + src.carry[2], max_blocks)
-                          for f, src in enumerate(sources)]
-            prof["bam_carry_bytes"] = prof.get("bam_carry_bytes", 0) + sum(int(x["carry_len"]) for x in inputs)
-        if bam_reader is not None and not all(x["eof"] for x in inputs):
-            def ahead_job(slot=which ^ 1, grow=grow):
-                for f, src in enumerate(sources):
-                    src.read_ahead(bamdev, slot, f, bam_reader, grow)
-            bam_ahead[0] = bam_ahead_pool.submit(ahead_job)
-        with prof("strip"):
-            blk = bamdev.run(which, inputs, score_mode, paired, paired, min(FILE_MAX_RECORDS, raw_cap // 36 + 2), wait_raw=False,
-                             skip_repeated=skip_repeated)
-            prof["strip_upload_ms"] = prof.get("strip_upload_ms", 0.0) + blk.ms_inflate
-            prof["strip_kernels_ms"] = prof.get("strip_kernels_ms", 0.0) + blk.ms_kernels
-        if blk.bad_block:
-            what = {1: "a BGZF block fails its decoder or its CRC-32", 2: "a file ends inside an alignment record",
-                    3: "a malformed alignment record"}.get(blk.bad_block, "damaged")
-            raise ValueError("corrupt BAM input: %s (%s, %s)" % (what, path1, path2))
-        eofs = [bool(x["eof"]) for x in inputs]
-        # which way each window went, for the profile (and the tests: tests/test_file_path.py, test_bam_gpu.py): "raw" = the whole
-        # inflated windows came back for the host to walk or print, "device_text" / "host_text" = who printed the wanted records
-        prof["bam_windows"] = prof.get("bam_windows", 0) + 1
-        if blk.unaligned or blk.weird or (cigar_mode and blk.n_exceptions):
-            prof["bam_windows_raw"] = prof.get("bam_windows_raw", 0) + 1
-            # (--cigar_scores: an NM or XS value the kernels do not vouch for sends the window the same way, as on the SAM path)
-            with prof("parse"):
-                # the whole windows as text, then the text rules (exactly the host path's semantics for this window)
-                bamdev.fetch_raw(which, blk)
-                bamdev.raw_wait(which)                               # the inflated bytes must have arrived
-                texts, tables = [], []
-                for f in (0, 1):
-                    # the record chain followed on the host (the inflated bytes are here already): every complete record
-                    rec = np.empty(blk.raw_len[f] // 36 + 2, dtype=np.uint32)
-                    first = inputs[f]["skip"] if not inputs[f]["carry_len"] else 0
-                    n_rec, stop = _host.bam_walk(blk.raw_addr[f], blk.raw_len[f], first, rec)
-                    rec = rec[:n_rec]
-                    text, loff, _llen, got = print_records(which, f, blk.raw_addr[f], rec.ctypes.data, n_rec)
-                    texts.append((text, got))
-                    tables.append((rec, stop, loff[:n_rec]))
-                    sources[f].ran(which, blk.raw_len[f], rec, stop)
-                whole = [eofs[f] and tables[f][1] == blk.raw_len[f] for f in (0, 1)]
-                hb = parsers[which].parse(texts[0][0], 0, texts[0][1], whole[0], texts[1][0], 0, texts[1][1], whole[1],
-                                          score_mode, paired, skip_repeated, paired, FILE_MAX_RECORDS)
-                if out_bam:
-                    # pair k of the text rules' walk is the record whose printed line begins where the parser's line k does
-                    # (under the skipping walk not record k)
-                    hb.bam_src = ([_ffi._host_view(blk.raw_addr[f], max(blk.raw_len[f], 1), np.uint8) for f in (0, 1)],
-                                  [tables[f][0][np.searchsorted(tables[f][2], hb.line_off[f][:hb.n])] for f in (0, 1)])
-            return hb, [texts[0][0], texts[1][0]], [0, 0], eofs
-        for f in (0, 1):
-            sources[f].ran(which, blk.raw_len[f], consumed=blk.consumed[f] - inputs[f]["skip"], records=max(blk.n - (1 if paired else 0), 0))
-        texts = [None, None]
-        if blk.n and not blk.n_exceptions:
-            # the fused pass right behind the strip kernels, on the slot's stream, BEFORE the next window's inflate launch is
-            # queued (issued later, from the main thread, it waits behind that launch: 25-30 ms a window)
-            with prof("classify"):
-                blk.classified = bamdev.classify(which, mode, blk.n, _floor_min_score(min_score))
-                # the bins are on the device: only the records a sink takes come back, packed (half of a window)
-                mask = sum(1 << b for b in range(6) if sinks[b])
-                blk.lines = None
-                blk.bins = None
-                if out_bam:
-                    # the six outputs as BAM: the records as they stand, gathered and framed on the device -- nothing is printed
-                    if bam_out_on_device:
-                        # (bam_compress: every member deflated on the device as well -- ordinary compressed BAM)
-                        fetch = bamdev.fetch_bins_bamz if bam_compress else bamdev.fetch_bins_bam
-                        bins = fetch(which, blk.n, paired, mask, 0, ref_shift)
-                        if bins[0] == 0:
-                            blk.bins = bins
-                    # (status 2 -- more bytes than the slot's buffers hold -- or XENOMAPPER_GPU_BAM_BINS=0: the packed records
-                    # come back and the host assembles)
-                    if blk.bins is None:
-                        blk.packed = bamdev.fetch_wanted(which, blk.n, paired, mask)
-                    key = (("bam_windows_device_bamz_bins" if bam_compress else "bam_windows_device_bam_bins") if blk.bins is not None
-                           else "bam_windows_host_bam")
-                else:
-                    if bam_bins_on_device[0]:
-                        # the six outputs themselves, gathered on the device: what comes back is what the sinks get
-                        bins = bamdev.fetch_bins(which, blk.n, paired, mask)
-                        if bins[0] == 0:
-                            blk.bins = bins
-                            prof["bam_windows_device_bins"] = prof.get("bam_windows_device_bins", 0) + 1
-                    if blk.bins is None and bam_text_on_device[0]:
-                        lines = bamdev.fetch_text(which, blk.n, paired, mask)
-                        if lines[0] == 0:
-                            blk.lines = lines
-                        # (status 1: a binary64 field -- f and B:f are printed on the device since round 6 --, 2: more text than the
-                        # slot's buffers hold: the host prints THIS window; the next one is offered to the device again)
-                    if blk.lines is None and blk.bins is None:
-                        blk.packed = bamdev.fetch_wanted(which, blk.n, paired, mask)
-                    key = "bam_windows_device_text" if (blk.lines is not None or blk.bins is not None) else "bam_windows_host_text"
-                prof[key] = prof.get(key, 0) + 1
-        else:
-            prof["bam_windows_raw"] = prof.get("bam_windows_raw", 0) + 1
-            bamdev.fetch_raw(which, blk)                                  # values the text rules must decide, or nothing: the whole windows
-
-        def finish():
-            # the records' SAM text, printed by the host threads when the block is settled -- in the main thread, while the
-            # helper thread has the GPU inflate and strip the NEXT window (printing here instead would put the two in a row)
-            with prof("parse"):
-                t_w = time.perf_counter()
-                bamdev.raw_wait(which)                               # the copy of the window ran beside the kernels and the next window's inflate
-                prof["bam_wait_raw"] = prof.get("bam_wait_raw", 0.0) + time.perf_counter() - t_w
-                if getattr(blk, "bins", None) is not None:          # gathered on the device: the outputs themselves are here
-                    return
-                if out_bam and blk.packed is not None:              # BAM outputs: the wanted records, packed -- the host assembles
-                    raw_addr, places, nbytes = blk.packed
-                    blk.bam_src = ([_ffi._host_view(raw_addr[f], max(nbytes[f], 1), np.uint8) for f in (0, 1)], list(places))
-                    return
-                if out_bam:                                          # ... or the whole windows and the table of the yielded records
-                    blk.bam_src = ([_ffi._host_view(blk.raw_addr[f], max(blk.raw_len[f], 1), np.uint8) for f in (0, 1)],
-                                   [_ffi._host_view(blk.rec_off_addr[f], max(blk.n, 1), np.uint32) for f in (0, 1)])
-                if getattr(blk, "lines", None) is not None:         # printed on the device: the text and its line table are here
-                    _st, text, loff, llen = blk.lines
-                    texts[0], texts[1] = text[0], text[1]
-                    blk.set_text(list(loff), list(llen))
-                    return
-                loffs, llens = [], []
-                # A unit's lines come from ONE file (primary bins: file 1, secondary bins: file 2, unresolved: both; :423-448),
-                # and a bin without a sink prints nothing: with the bins known on the device, only those records came back
-                # (packed; their table says where each went), and only those are printed
-                wanted = [None, None]
-                raw_addr, off_addr = blk.raw_addr, blk.rec_off_addr
-                if blk.packed is not None:
-                    raw_addr, places, _bytes = blk.packed
-                    off_addr = [places[0].ctypes.data if blk.n else 0, places[1].ctypes.data if blk.n else 0]
-                    wanted = [(places[f] != 0xFFFFFFFF).view(np.uint8) for f in (0, 1)]
-                t_p = time.perf_counter()
-                for f in (0, 1):
-                    text, loff, llen, _got = print_records(which, f, raw_addr[f], off_addr[f], blk.n, sparse=True,
-                                                           wanted=wanted[f])
-                    texts[f] = text
-                    loffs.append(loff); llens.append(llen)
-                prof["bam_print"] = prof.get("bam_print", 0.0) + time.perf_counter() - t_p
-                blk.set_text(loffs, llens)
-        blk.finish = finish
-        return blk, texts, [0, 0], eofs
-
-    def drop_stripper():
-        """The stripper is given up for the rest of the run (and of the process)."""
-        nonlocal stripper
-        _forget_stripper(stripper)
-        stripper = None
-
-    def parse_next(which, want):
-        nonlocal stripper
-        if bamdev is not None:
-            return parse_next_bamdev(which, want)
-        with prof("window"):
-            wins = [src.window(want) for src in sources]
-        if stripper is not None and max(w[2] for w in wins) <= _ffi.STRIP_MAX_WINDOW:
-            # no line of a record is shorter than two bytes with its terminator
-            records = min(FILE_MAX_RECORDS, max(w[2] for w in wins) // 2 + 2)
-            try:
-                stripper.reserve(which, max(w[2] for w in wins), records)
-            except MemoryError:                                      # page-locked or device memory ran out: the host threads strip
-                drop_stripper()
-        blk = None
-        if stripper is not None and max(w[2] for w in wins) <= _ffi.STRIP_MAX_WINDOW:
-            try:
-                with prof("stage"):
-                    # read(2) into page-locked memory, piece by piece: the upload of one piece hides the read of the next; no
-                    # page of the inputs is mapped, and the writer gathers its lines from the staging buffer
-                    for f, w in enumerate(wins):
-                        base = stripper.staging_address(which, f)
-                        for at in range(0, w[2], STAGE_PIECE):
-                            piece = min(STAGE_PIECE, w[2] - at)
-                            parsers[which].pread(sources[f].fileno(), w[1] + at, base + at, piece)
-                            stripper.upload(which, f, at, piece)
-                with prof("strip"):
-                    blk = stripper.run(which, wins[0][2], wins[0][3], wins[1][2], wins[1][3], score_mode, paired,
-                                       skip_repeated, paired, records)
-                    prof["strip_upload_ms"] = prof.get("strip_upload_ms", 0.0) + blk.ms_upload
-                    prof["strip_kernels_ms"] = prof.get("strip_kernels_ms", 0.0) + blk.ms_kernels
-            except (MemoryError, OSError):
-                # the --cigar_scores arrays did not fit (MemoryError from the run), or a read into the staging buffer failed
-                # half way: this window and the rest of the run go through the host stripper, and the half-staged stripper
-                # is not kept for later runs of the process
-                drop_stripper()
-                blk = None
-        if blk is not None:
-            if blk.non_ascii:
-                raise _host.NonAsciiInput()
-            if (sam_bins_on_device and blk.n and not blk.n_exceptions and not blk.overflow):
-                # the fused pass right behind the strip kernels, then the six outputs gathered on the device and sent back as one
-                # stream (xm_strip_fetch_bins): the main thread writes six byte ranges instead of gathering the lines.  A window
-                # with a wanted line that needs re-joining, or with more text than the buffers hold, is written as before.
-                with prof("classify"):
-                    blk.classified = stripper.classify(which, mode, blk.n, _floor_min_score(min_score))
-                    mask = sum(1 << b for b in range(6) if sinks[b])
-                    bins = stripper.fetch_bins(which, blk.n, paired, mask)
-                if bins[0] == 0:
-                    blk.bins = bins
-                    prof["sam_windows_device_bins"] = prof.get("sam_windows_device_bins", 0) + 1
-
-                    def finish(strip=stripper, slot=which):
-                        t_w = time.perf_counter()
-                        strip.out_wait(slot)
-                        prof["sam_wait_out"] = prof.get("sam_wait_out", 0.0) + time.perf_counter() - t_w
-                    blk.finish = finish
-            prof["sam_windows"] = prof.get("sam_windows", 0) + 1
-            staged = [stripper.staging(which, f) for f in (0, 1)]
-            if blk.overflow or (cigar_mode and blk.n_exceptions):
-                # more lines than the device tables hold, or a --cigar_scores block with a value the kernels do not vouch for:
-                # this window goes through the host stripper (the text is in the staging buffers already)
-                with prof("parse"):
-                    blk = parsers[which].parse(staged[0], 0, wins[0][2], wins[0][3], staged[1], 0, wins[1][2], wins[1][3],
-                                               score_mode, paired, skip_repeated, paired, FILE_MAX_RECORDS)
-            return blk, staged, [0, 0], [w[3] for w in wins]
-        with prof("parse"):
-            blk = None
-            if bam and all(src.pre_ok for src in sources):
-                # BAM holds AS / XS / ZS / NM as typed values and the CIGAR as operations: the decoder described every line
-                # it printed, the stripper only walks the two files in lock-step (no tokenising of its own output)
-                pw = [src.pre_window() for src in sources]
-                blk = parsers[which].parse_pre(wins[0][0], wins[0][1], wins[0][2], wins[0][3], pw[0][0], pw[0][1],
-                                               wins[1][0], wins[1][1], wins[1][2], wins[1][3], pw[1][0], pw[1][1],
-                                               score_mode, paired, skip_repeated, paired, FILE_MAX_RECORDS)
-            if blk is None:                                       # SAM input, or a line that needs the text rules
-                blk = parsers[which].parse(wins[0][0], wins[0][1], wins[0][2], wins[0][3], wins[1][0], wins[1][1], wins[1][2],
-                                           wins[1][3], score_mode, paired, skip_repeated, paired, FILE_MAX_RECORDS)
-        return blk, [w[0] for w in wins], [w[1] for w in wins], [w[3] for w in wins]
-
-    def settle(block, raws, pos, parser, pending):
-        """Classify one parsed block and hand its units to the sinks.  Returns the input error to raise once the
-        units in front of it have been written (one found while resolving the stripper's exceptions comes first)."""
-        if getattr(block, "finish", None) is not None:
-            block.finish()                                       # GPU BAM path: print the records' text now
-        n = block.n
-        on_device = isinstance(block, (_ffi.StrippedBlock, _ffi.BamDevBlock))
-        exc = block.exc
-        patches, bad, err = {}, None, None
-        if exc:
-            flags = np.unpackbits(block.unit_bits.view(np.uint8), bitorder="little")[:n].astype(bool)
-            if paired:
-                needed = flags.copy()
-                needed[:-1] |= flags[1:]
+                self.bamdev = default_bamdev()
+            except MemoryError:
+                self.bamdev = None
+        if out_bam and self.bamdev is None:
+            raise RuntimeError("BAM outputs need the GPU BAM front end (BAM inputs, a min_score that is a number, XENOMAPPER_GPU_BAM "
+                               "not 0, and memory for its buffers)")
+        with self.prof("open"):
+            if self.bamdev is not None:
+                self.sources = [_GpuBamFile(path, n_threads) for path in (path1, path2)]
             else:
-                needed = np.ones(n, dtype=bool)
-            patches, bad, err = _resolve_exceptions(block, raws, pos, needed, tag_func, cigar_mode)
-        if err is not None:
-            n, pending = bad, err                                # units closing at index >= bad are not reached
-        ready = getattr(block, "bins", None) if (not exc and err is None) else None
-        if on_device and block.n and ready is None and block.tables is not None:
-            parser.adopt_lines(raws[0], pos[0], raws[1], pos[1], block.n, block.tables)
-        if n:
-            with prof("classify"):          # one fused pass: category bytes, counts and the six bin lists
-                if on_device and not patches and n == block.n and getattr(block, "classified", None) is not None:
-                    code, idx, off, counts = block.classified        # classified right behind the strip kernels (GPU BAM path)
-                elif on_device and not patches:                  # the columns never left the device
-                    code, idx, off, counts = block.stripper.classify(block.slot, mode, n, _floor_min_score(min_score))
-                else:
-                    code, idx, off, counts = _classify_parsed(ctx, mode, block, n, patches, cigar_mode, min_score)
-            limit, state_error = None, None
-            if int(off[7]) != int(off[6]):                       # a unit fell through every branch (ref :289)
-                limit = int(idx[int(off[6]):int(off[7])].min())
-                j = limit - 1 if (paired and (int(code[limit]) >> 3) > 5) else limit    # the mate that fell through, as _run()
-                shown = []
-                for f in (0, 1):                                 # the values the reference would print: the plugin's own
-                    fields = _fields_of(raws[f], block, f, j, pos[f])
-                    shown += [tag_func(fields, tag="AS"), tag_func(fields, tag="XS")]
-                state_error = RuntimeError("Error in processing logic with values {0} ".format(tuple(shown)))
-            if ready is not None and limit is not None:          # (state 6 needs a NaN: not on the int32 columns of this path)
-                raise RuntimeError("a unit fell through every branch on the GPU BAM path")
-            if ready is not None and limit is None:
-                # the outputs were gathered on the device (xm_bamdev_fetch_bins / xm_strip_fetch_bins): six byte ranges, written
-                # as they stand (into a regular file's pages by the writer's threads, else through the sink)
-                _st, text, boff = ready
-                for b in range(6):
-                    if sinks[b] and boff[b + 1] > boff[b]:
-                        piece = text[boff[b]:boff[b + 1]]
-                        if out_bam:                              # what crossed the link is what is written: the framed members
-                            prof["bam_out_bytes"] = prof.get("bam_out_bytes", 0) + int(boff[b + 1] - boff[b])
-                        with prof("emit"):
-                            done = _emit_into_file(parser, paired, b, None, sinks[b], ahead, ahead_pool, ready=piece)
-                        if not done:
-                            with prof("write"):
-                                _write_bytes(sinks[b], piece)
-            for b in (range(6) if (out_bam and (ready is None or limit is not None)) else ()):
-                if sinks[b]:
-                    # BAM outputs of a window the device did not gather: the same records through the host assembler
-                    seg = idx[int(off[b]):int(off[b + 1])]
-                    if limit is not None:
-                        seg = seg[seg < limit]
-                    with prof("emit"):
-                        data = _bgzf_frame(_bam_records_of(seg, paired, b, block.bam_src[0], block.bam_src[1], ref_shift), 1)
-                    prof["bam_out_bytes"] = prof.get("bam_out_bytes", 0) + len(data)
-                    with prof("write"):
-                        _write_bytes(sinks[b], data)
-            for b in (range(6) if (distinct and not out_bam and (ready is None or limit is not None)) else ()):
-                if sinks[b]:
-                    seg = idx[int(off[b]):int(off[b + 1])]
-                    if limit is not None:
-                        seg = seg[seg < limit]
-                    with prof("emit"):
-                        done = _emit_into_file(parser, paired, b, seg, sinks[b], ahead, ahead_pool)
-                        text = None if done else parser.emit(paired, b, seg, reuse=True)
-                    with prof("write"):
-                        _write_bytes(sinks[b], text)
-            if not distinct:
-                _emit_shared(parser, paired, code, idx, off, sinks, limit)
-            if state_error is not None:
-                raise state_error
-            _add_counts(totals, key_order, paired, code, counts)
-        return pending
+                self.sources = [(_BamSource(path, n_threads) if bam else _SamSource(path, None if starts is None else starts[k]))
+                                for k, path in enumerate((path1, path2))]
+            # Two parsers alternate so that the next window is decoded (BAM) and parsed in a helper thread -- the C++
+            # code runs without the GIL -- while the GPU classifies and the writer emits the current one.
+            self.parsers = [_host.Parser(n_threads), _host.Parser(n_threads)]
+            self.pool = ThreadPoolExecutor(max_workers=1)
+            self.future = None                                       # the next window, being parsed by the helper thread
+            # output files extended ahead of the writer, their pages unmapped behind it (more helper threads than two measured no
+            # better: profiles/r06_ab_sam_bins.txt)
+            self.ahead = {}
+            self.ahead_pool = ThreadPoolExecutor(max_workers=max(1, int(os.environ.get("XENOMAPPER_AHEAD_THREADS", "2"))))
+        self.totals, self.key_order = Counter(), []
+        self.window = FILE_WINDOW_BYTES
+        self.active = [s for s in sinks if s]
+        self.distinct = len(set(id(s) for s in self.active)) == len(self.active)
+        self.sink_mask = sum(1 << b for b in range(6) if sinks[b])   # the bins whose units a front end sends back
+        # SAM text: the text itself goes to the GPU and is split there (include/xenomapper_strip.h) -- the host threads only copy
+        # windows into page-locked memory and write the outputs.  XENOMAPPER_GPU_STRIP=0 keeps the host stripper.
+        self.stripper = None
+        if not bam and min_score == min_score and os.environ.get("XENOMAPPER_GPU_STRIP", "1") != "0":
+            try:
+                self.stripper = default_stripper()
+            except MemoryError:                                      # no room for its buffers: the host threads strip
+                self.stripper = None
+        # SAM text: the outputs gathered on the device as well (every bin needs a sink of its own; XENOMAPPER_GPU_SAM_BINS=0: the host gathers)
+        self.sam_bins_on_device = (self.stripper is not None and self.distinct
+                                   and os.environ.get("XENOMAPPER_GPU_SAM_BINS", "1") != "0")
+        self.bam_text = _BAM_TEXT_BUFFERS                            # (slot, file) -> [text bytes, line_off, line_len] of the GPU BAM path
+        self.bam_windows = 0                                         # windows run so far
+        # the records' SAM text is printed on the device when the reference names could be read (XENOMAPPER_GPU_BAM_TEXT=0: by the
+        # host threads, from the packed records; a window with floating-point fields is printed that way in any case)
+        self.bam_text_on_device = False
+        self.ref_shift = 0                                           # BAM outputs: file 2's reference ids in `unresolved` (its list follows file 1's)
+        if out_bam and sinks[4]:
+            if self.sources[0].ref_names is None:
+                raise ValueError("the reference list of %s could not be read: `unresolved` cannot be written as BAM" % path1)
+            self.ref_shift = len(self.sources[0].ref_names)
+        if (self.bamdev is not None and not out_bam and os.environ.get("XENOMAPPER_GPU_BAM_TEXT", "1") != "0"
+                and all(src.ref_names is not None for src in self.sources)):
+            for f, src in enumerate(self.sources):
+                self.bamdev.set_refs(f, src.ref_names)
+            self.bam_text_on_device = True
+        # ... and gathered there into the six outputs (xm_bamdev_fetch_bins: the host writes six byte ranges per window instead of
+        # gathering the lines; needs every bin to have a sink of its own -- two bins sharing one are written unit by unit, _emit_shared).
+        # XENOMAPPER_GPU_BAM_BINS=0: the device prints, the host gathers (round 5's form)
+        bam_bins = os.environ.get("XENOMAPPER_GPU_BAM_BINS", "1") != "0"
+        self.bam_bins_on_device = self.bam_text_on_device and self.distinct and bam_bins
+        # BAM outputs: records gathered and framed on the device (xm_bamdev_fetch_bins_bam; XENOMAPPER_GPU_BAM_BINS=0: the packed records
+        # come back and the host assembles)
+        self.bam_out_on_device = out_bam and bam_bins
+        # the GPU BAM path reads the next window's compressed blocks while the GPU works on the current one (_GpuBamFile.read_ahead):
+        # a reader of its own (8 threads: pread into page-locked memory peaks there, e2e.host_ceilings) and one thread that drives it
+        self.bam_reader = (_host.Parser(8) if self.bamdev is not None and os.environ.get("XENOMAPPER_BAM_READ_AHEAD", "1") != "0"
+                           else None)
+        self.bam_ahead_pool = ThreadPoolExecutor(max_workers=1) if self.bam_reader is not None else None
+        self.bam_ahead = None                                        # the last job given to that thread: the read-ahead in flight
+        self.bam_comp_worst_case = False                             # a window's compressed bytes outgrew the staging reserved for half the inflated size
 
-    which = 0
-    future = None
-    try:
+    # ---- the window loop
+
+    def run(self):
+        """The window loop: the helper thread parses the next window while this thread classifies and writes the current one."""
+        from . import _host
+        which = 0
         while True:
             try:
-                if future is not None:
-                    parsed, future = future.result(), None
+                if self.future is not None:
+                    win, self.future = self.future.result(), None
                 else:
-                    parsed = parse_next(which, window)
+                    win = self.parse_next(which, self.window)
             except _host.NonAsciiInput:
-                if bam:
+                if self.bam:
                     raise ValueError("non-ASCII bytes in BAM text fields are not supported")
-                return _finish_in_python(mode, path1, path2, [src.pos for src in sources], sinks, min_score, tag_func,
-                                         skip_repeated, totals, key_order)
-            block, raws, pos, eofs = parsed
+                return _finish_in_python(self.mode, self.paths[0], self.paths[1], [src.pos for src in self.sources], self.sinks,
+                                         self.min_score, self.tag_func, self.skip_repeated, self.totals, self.key_order)
+            block, eofs = win.block, win.eofs
             progressed = block.consumed[0] > 0 or block.consumed[1] > 0
             if block.starved and not progressed and not (eofs[0] and eofs[1]):
-                window *= 2                                      # a line (or run of equal names) longer than the window
+                self.window *= 2                                 # a line (or run of equal names) longer than the window
                 continue
             pending = AssertionError() if block.mismatch_at >= 0 else None
             last = block.ended or pending is not None or (eofs[0] and eofs[1] and not progressed)
             if not last:
                 for f in (0, 1):
-                    sources[f].advance(block.consumed[f], block.consumed_lines[f])
-                future = pool.submit(parse_next, which ^ 1, window)   # parse the next window while this one is classified
-            pending = settle(block, raws, pos, parsers[which], pending)
+                    self.sources[f].advance(block.consumed[f], block.consumed_lines[f])
+                self.future = self.pool.submit(self.parse_next, which ^ 1, self.window)   # parse the next window while this one is classified
+            pending = self.settle(win, self.parsers[which], pending)
             if pending is not None:
                 raise pending
             if last:
-                break
+                return _ordered_counts(self.totals, self.key_order)
             which ^= 1
-    finally:
-        if future is not None:
+
+    def close(self):
+        """Await the helper threads, cut the output files back to their content, close inputs and parsers, publish the profile.
+        Trouble with an output file is raised only when nothing else is being raised."""
+        prof = self.prof
+        if self.future is not None:
             try:
-                future.result()
+                self.future.result()
             except Exception:
                 pass
         with prof("close"):
             trouble = None
-            for sink in active:                                      # cut the output files back to their content
-                state = ahead.pop(id(sink), None)
+            for sink in self.active:                                 # cut the output files back to their content
+                state = self.ahead.pop(id(sink), None)
                 if state is not None:
                     try:
-                        state.finish(sink, ahead_pool)
+                        state.finish(sink, self.ahead_pool)
                     except OSError as exc:
                         trouble = trouble or exc
-            ahead_pool.shutdown(wait=True)
-            pool.shutdown(wait=True)
-            if bam_ahead_pool is not None:
-                bam_ahead_pool.shutdown(wait=True)
-                bam_reader.close()
-            for prs in parsers:
+            self.ahead_pool.shutdown(wait=True)
+            self.pool.shutdown(wait=True)
+            if self.bam_ahead_pool is not None:
+                self.bam_ahead_pool.shutdown(wait=True)
+                self.bam_reader.close()
+            for prs in self.parsers:
                 prs.close()
-            for src in sources:
-                if hasattr(src, "ahead_hits"):
-                    prof["bam_ahead_hits"] = prof.get("bam_ahead_hits", 0) + src.ahead_hits
-                    prof["bam_ahead_misses"] = prof.get("bam_ahead_misses", 0) + src.ahead_misses
+            for src in self.sources:
+                if self.bamdev is not None:
+                    prof.add("bam_ahead_hits", src.ahead_hits)
+                    prof.add("bam_ahead_misses", src.ahead_misses)
                 src.close()
-        total = time.perf_counter() - t_all
+        total = time.perf_counter() - self.t_all
         prof["other"] = total - sum(v for k, v in prof.items() if not k.endswith("_ms") and not k.startswith("bam_") and not k.startswith("sam_"))   # negative: helper-thread phases overlap the rest
         LAST_FILE_PROFILE.clear()
         LAST_FILE_PROFILE.update(prof, total=total)
@@ -2133,10 +1836,456 @@ def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_
             print("xenomapper file path: %.3f s  " % total + "  ".join("%s %.3f" % kv for kv in prof.items()), file=sys.stderr)
         if trouble is not None and sys.exc_info()[0] is None:
             raise trouble
-    ordered = Counter()
-    for key in key_order:
-        ordered[key] = totals[key]
-    return ordered
+
+    def parse_next(self, which, want):
+        """One window of both inputs through slot `which` -> _Window."""
+        if self.bamdev is not None:
+            return self._bam_window(which, want)
+        with self.prof("window"):
+            wins = [src.window(want) for src in self.sources]
+        win = None
+        if self.stripper is not None and max(w[2] for w in wins) <= _ffi.STRIP_MAX_WINDOW:
+            win = self._stripped_window(which, wins)
+        return win if win is not None else self._parsed_window(which, wins)
+
+    # ---- SAM text, or BAM decoded by the host
+
+    def _drop_stripper(self):
+        """The stripper is given up for the rest of the run (and of the process)."""
+        _forget_stripper(self.stripper)
+        self.stripper = None
+
+    def _stripped_window(self, which, wins):
+        """The windows `wins` of the two SAM files through the GPU stripper -> _Window, or None when the stripper had to be given
+        up: the host stripper then takes this window and the rest of the run."""
+        from . import _host
+        prof, stripper = self.prof, self.stripper
+        size = max(w[2] for w in wins)
+        # no line of a record is shorter than two bytes with its terminator
+        records = min(FILE_MAX_RECORDS, size // 2 + 2)
+        try:
+            stripper.reserve(which, size, records)
+        except MemoryError:                                          # page-locked or device memory ran out: the host threads strip
+            self._drop_stripper()
+            return None
+        try:
+            with prof("stage"):
+                # read(2) into page-locked memory, piece by piece: the upload of one piece hides the read of the next; no
+                # page of the inputs is mapped, and the writer gathers its lines from the staging buffer
+                for f, w in enumerate(wins):
+                    base = stripper.staging_address(which, f)
+                    for at in range(0, w[2], STAGE_PIECE):
+                        piece = min(STAGE_PIECE, w[2] - at)
+                        self.parsers[which].pread(self.sources[f].fileno(), w[1] + at, base + at, piece)
+                        stripper.upload(which, f, at, piece)
+            with prof("strip"):
+                blk = stripper.run(which, wins[0][2], wins[0][3], wins[1][2], wins[1][3], self.score_mode, self.paired,
+                                   self.skip_repeated, self.paired, records)
+                prof.add("strip_upload_ms", blk.ms_upload)
+                prof.add("strip_kernels_ms", blk.ms_kernels)
+        except (MemoryError, OSError):
+            # the --cigar_scores arrays did not fit (MemoryError from the run), or a read into the staging buffer failed
+            # half way: this window and the rest of the run go through the host stripper, and the half-staged stripper
+            # is not kept for later runs of the process
+            self._drop_stripper()
+            return None
+        if blk.non_ascii:
+            raise _host.NonAsciiInput()
+        staged = [stripper.staging(which, f) for f in (0, 1)]
+        win = _Window(blk, staged, [0, 0], [w[3] for w in wins])
+        if (self.sam_bins_on_device and blk.n and not blk.n_exceptions and not blk.overflow):
+            # the fused pass right behind the strip kernels, then the six outputs gathered on the device and sent back as one
+            # stream (xm_strip_fetch_bins): the main thread writes six byte ranges instead of gathering the lines.  A window
+            # with a wanted line that needs re-joining, or with more text than the buffers hold, is written as before.
+            with prof("classify"):
+                win.classified = stripper.classify(which, self.mode, blk.n, _floor_min_score(self.min_score))
+                bins = stripper.fetch_bins(which, blk.n, self.paired, self.sink_mask)
+            if bins[0] == 0:
+                win.bins = bins
+                prof.add("sam_windows_device_bins", 1)
+                win.finish = self._await_sam_bins
+        prof.add("sam_windows", 1)
+        if blk.overflow or (self.cigar_mode and blk.n_exceptions):
+            # more lines than the device tables hold, or a --cigar_scores block with a value the kernels do not vouch for:
+            # this window goes through the host stripper (the text is in the staging buffers already)
+            with prof("parse"):
+                win.block = self.parsers[which].parse(staged[0], 0, wins[0][2], wins[0][3], staged[1], 0, wins[1][2], wins[1][3],
+                                                      self.score_mode, self.paired, self.skip_repeated, self.paired,
+                                                      FILE_MAX_RECORDS)
+        return win
+
+    def _await_sam_bins(self, win):
+        """settle's first step for a window whose outputs the stripper gathered: their copy to the host must have arrived."""
+        t_w = time.perf_counter()
+        win.block.stripper.out_wait(win.block.slot)
+        self.prof.add("sam_wait_out", time.perf_counter() - t_w)
+
+    def _parsed_window(self, which, wins):
+        """The windows `wins` through the host threads: BAM by the decoder's line descriptions, SAM (or a line that needs them)
+        by the text rules."""
+        parser = self.parsers[which]
+        with self.prof("parse"):
+            blk = None
+            if self.bam and all(src.pre_ok for src in self.sources):
+                # BAM holds AS / XS / ZS / NM as typed values and the CIGAR as operations: the decoder described every line
+                # it printed, the stripper only walks the two files in lock-step (no tokenising of its own output)
+                pw = [src.pre_window() for src in self.sources]
+                blk = parser.parse_pre(wins[0][0], wins[0][1], wins[0][2], wins[0][3], pw[0][0], pw[0][1],
+                                       wins[1][0], wins[1][1], wins[1][2], wins[1][3], pw[1][0], pw[1][1],
+                                       self.score_mode, self.paired, self.skip_repeated, self.paired, FILE_MAX_RECORDS)
+            if blk is None:                                       # SAM input, or a line that needs the text rules
+                blk = parser.parse(wins[0][0], wins[0][1], wins[0][2], wins[0][3], wins[1][0], wins[1][1], wins[1][2],
+                                   wins[1][3], self.score_mode, self.paired, self.skip_repeated, self.paired, FILE_MAX_RECORDS)
+        return _Window(blk, [w[0] for w in wins], [w[1] for w in wins], [w[3] for w in wins])
+
+    # ---- BAM on the GPU
+
+    def _print_records(self, which, f, raw_addr, rec_off_addr, n, sparse=False, wanted=None):
+        """SAM text of records [0, n) of a window decoded on the GPU -> (text array, line_off, line_len)."""
+        buf = self.bam_text.get((which, f))
+        if buf is None or buf[1].shape[0] < n:
+            text = buf[0] if buf is not None else np.empty(1 << 20, dtype=np.uint8)
+            buf = self.bam_text[(which, f)] = [text, np.empty(n + n // 4 + 64, dtype=np.uint32), np.empty(n + n // 4 + 64, dtype=np.uint32)]
+        while True:
+            got = self.sources[f].reader.print_records(raw_addr, rec_off_addr, n, buf[0], buf[1], buf[2], sparse, wanted)
+            if got >= 0:
+                return buf[0], buf[1], buf[2], got
+            buf[0] = np.empty(-got + (-got >> 3) + (1 << 16), dtype=np.uint8)
+
+    def _bam_window(self, which, want):
+        """One window of both BAM files on the GPU: stage compressed blocks, xm_bamdev_run (inflate, CRC, record chain, strip,
+        pair), print the records' text for the writer.  A window the device does not vouch for -- blocks that do not begin
+        with a record, a record the text rules might read differently -- is printed whole and stripped by the text rules."""
+        prof, sources, bamdev = self.prof, self.sources, self.bamdev
+        with prof("window"):
+            self._await_read_ahead()
+            sizes = _bam_window_sizes(max(want, BAM_GPU_WINDOW_BYTES), self.bam_windows, max(src.carry[2] for src in sources),
+                                      max(src.data.shape[0] - src.cursor for src in sources), self.bam_comp_worst_case)
+            self.bam_windows += 1
+            inputs = self._stage_bam_window(which, sizes)
+            prof.add("bam_carry_bytes", sum(int(x["carry_len"]) for x in inputs))
+        if self.bam_reader is not None and not all(x["eof"] for x in inputs):
+            def ahead_job(slot=which ^ 1, grow=sizes.grow):
+                for f, src in enumerate(sources):
+                    src.read_ahead(bamdev, slot, f, self.bam_reader, grow)
+            self.bam_ahead = self.bam_ahead_pool.submit(ahead_job)
+        with prof("strip"):
+            blk = bamdev.run(which, inputs, self.score_mode, self.paired, self.paired, sizes.max_records, wait_raw=False,
+                             skip_repeated=self.skip_repeated)
+            prof.add("strip_upload_ms", blk.ms_inflate)
+            prof.add("strip_kernels_ms", blk.ms_kernels)
+        if blk.bad_block:
+            what = {1: "a BGZF block fails its decoder or its CRC-32", 2: "a file ends inside an alignment record",
+                    3: "a malformed alignment record"}.get(blk.bad_block, "damaged")
+            raise ValueError("corrupt BAM input: %s (%s, %s)" % (what, self.paths[0], self.paths[1]))
+        eofs = [bool(x["eof"]) for x in inputs]
+        # which way each window went, for the profile (and the tests: tests/test_file_path.py, test_bam_gpu.py): "raw" = the whole
+        # inflated windows came back for the host to walk or print, "device_text" / "host_text" = who printed the wanted records
+        prof.add("bam_windows", 1)
+        if blk.unaligned or blk.weird or (self.cigar_mode and blk.n_exceptions):
+            # (--cigar_scores: an NM or XS value the kernels do not vouch for sends the window the same way, as on the SAM path)
+            return self._bam_window_by_text_rules(which, blk, inputs, eofs)
+        return self._bam_window_on_device(which, blk, inputs, eofs)
+
+    def _await_read_ahead(self):
+        """The helper thread's last job -- the read-ahead into this slot's staging buffers, or the first window's reserve of
+        this slot -- has ended before the slot is reserved and staged."""
+        if self.bam_ahead is not None:
+            try:
+                self.bam_ahead.result()
+            except Exception:                                        # noqa: BLE001 -- a failed read or copy ahead: stage() does it all
+                for src in self.sources:
+                    src.ahead = None
+            self.bam_ahead = None
+
+    def _stage_bam_window(self, which, sizes):
+        """Reserve slot `which` for a window of `sizes` and stage both files' next blocks into it -> the two inputs of
+        xm_bamdev_run.  Staging reserved for half the inflated size that the compressed bytes outgrow is reserved again, once, for
+        the worst case."""
+        bamdev, sources = self.bamdev, self.sources
+        bamdev.reserve(which, sizes.comp_cap, sizes.raw_cap, sizes.max_blocks, sizes.max_records)
+        if self.bam_windows == 1 and self.bam_ahead_pool is not None and not all(src.at_end for src in sources):
+            # the run's first window: the OTHER slot's buffers are made now, by the helper thread, beside this window's work
+            # (page-locking them is a quarter of a process's first run; the read-ahead behind this window then has where to read to).
+            # The future is kept where the read-ahead's is: the next window's own reserve of that slot waits for it.
+            self.bam_ahead = self.bam_ahead_pool.submit(_quietly, bamdev.reserve, which ^ 1, sizes.comp_cap, sizes.raw_cap,
+                                                        sizes.max_blocks, sizes.max_records)
+        # the two files hold the same reads at different bytes per record: each gets a window in proportion, so that the
+        # windows hold about as many records and neither file drags a growing tail from window to window
+        per_rec = [src.bytes_per_record for src in sources]
+        scale = [p / max(per_rec) for p in per_rec] if min(per_rec) > 0 else [1.0, 1.0]
+
+        def stage():
+            return [src.stage(bamdev, which, f, self.parsers[which], int(sizes.want * scale[f]) + src.carry[2], sizes.max_blocks)
+                    for f, src in enumerate(sources)]
+        try:
+            return stage()
+        except _CompressedBytesOutgrowStaging:
+            self.bam_comp_worst_case = True
+            self.prof.add("bam_staging_regrown", 1)
+            bamdev.reserve(which, sizes.raw_cap, sizes.raw_cap, sizes.max_blocks, sizes.max_records)
+            for src in sources:
+                src.ahead = None                                     # (read into the buffers that were just replaced)
+            return stage()
+
+    def _bam_window_by_text_rules(self, which, blk, inputs, eofs):
+        """A window the device does not vouch for: the whole inflated windows come back, the host follows the record chain,
+        prints every record and parses the text (exactly the host path's semantics for this window)."""
+        from . import _host
+        bamdev = self.bamdev
+        self.prof.add("bam_windows_raw", 1)
+        with self.prof("parse"):
+            # the whole windows as text, then the text rules
+            bamdev.fetch_raw(which, blk)
+            bamdev.raw_wait(which)                                   # the inflated bytes must have arrived
+            texts, tables = [], []
+            for f in (0, 1):
+                # the record chain followed on the host (the inflated bytes are here already): every complete record
+                rec = np.empty(blk.raw_len[f] // 36 + 2, dtype=np.uint32)
+                first = inputs[f]["skip"] if not inputs[f]["carry_len"] else 0
+                n_rec, stop = _host.bam_walk(blk.raw_addr[f], blk.raw_len[f], first, rec)
+                rec = rec[:n_rec]
+                text, loff, _llen, got = self._print_records(which, f, blk.raw_addr[f], rec.ctypes.data, n_rec)
+                texts.append((text, got))
+                tables.append((rec, stop, loff[:n_rec]))
+                self.sources[f].ran(which, blk.raw_len[f], rec, stop)
+            whole = [eofs[f] and tables[f][1] == blk.raw_len[f] for f in (0, 1)]
+            hb = self.parsers[which].parse(texts[0][0], 0, texts[0][1], whole[0], texts[1][0], 0, texts[1][1], whole[1],
+                                           self.score_mode, self.paired, self.skip_repeated, self.paired, FILE_MAX_RECORDS)
+            win = _Window(hb, [texts[0][0], texts[1][0]], [0, 0], eofs)
+            if self.out_bam:
+                # pair k of the text rules' walk is the record whose printed line begins where the parser's line k does
+                # (under the skipping walk not record k)
+                win.bam_src = (self._inflated(blk),
+                               [tables[f][0][np.searchsorted(tables[f][2], hb.line_off[f][:hb.n])] for f in (0, 1)])
+        return win
+
+    @staticmethod
+    def _inflated(blk):
+        """The inflated bytes of both files of a window as arrays (for the host's BAM assembler)."""
+        return [_ffi._host_view(blk.raw_addr[f], max(blk.raw_len[f], 1), np.uint8) for f in (0, 1)]
+
+    def _bam_window_on_device(self, which, blk, inputs, eofs):
+        """A window the device vouches for: classify behind the strip kernels, then fetch what the sinks take.  A window with
+        values the text rules must decide (or with nothing) comes back whole instead."""
+        prof, bamdev = self.prof, self.bamdev
+        for f in (0, 1):
+            self.sources[f].ran(which, blk.raw_len[f], consumed=blk.consumed[f] - inputs[f]["skip"],
+                                records=max(blk.n - (1 if self.paired else 0), 0))
+        win = _Window(blk, [None, None], [0, 0], eofs)
+        win.finish = self._finish_bam_window
+        if blk.n and not blk.n_exceptions:
+            # the fused pass right behind the strip kernels, on the slot's stream, BEFORE the next window's inflate launch is
+            # queued (issued later, from the main thread, it waits behind that launch: 25-30 ms a window)
+            with prof("classify"):
+                win.classified = bamdev.classify(which, self.mode, blk.n, _floor_min_score(self.min_score))
+                # the bins are on the device: only the records a sink takes come back, packed (half of a window)
+                key = self._fetch_as_bam(which, win) if self.out_bam else self._fetch_as_sam(which, win)
+                prof.add(key, 1)
+        else:
+            prof.add("bam_windows_raw", 1)
+            bamdev.fetch_raw(which, blk)                             # values the text rules must decide, or nothing: the whole windows
+        return win
+
+    def _fetch_as_bam(self, which, win):
+        """The six outputs as BAM: the records as they stand, gathered and framed on the device -- nothing is printed.
+        -> the profile's counter for the way the window went."""
+        bamdev, n = self.bamdev, win.block.n
+        if self.bam_out_on_device:
+            # (bam_compress: every member deflated on the device as well -- ordinary compressed BAM)
+            fetch = bamdev.fetch_bins_bamz if self.bam_compress else bamdev.fetch_bins_bam
+            bins = fetch(which, n, self.paired, self.sink_mask, 0, self.ref_shift)
+            if bins[0] == 0:
+                win.bins = bins
+                return "bam_windows_device_bamz_bins" if self.bam_compress else "bam_windows_device_bam_bins"
+        # (status 2 -- more bytes than the slot's buffers hold -- or XENOMAPPER_GPU_BAM_BINS=0: the packed records
+        # come back and the host assembles)
+        win.packed = bamdev.fetch_wanted(which, n, self.paired, self.sink_mask)
+        return "bam_windows_host_bam"
+
+    def _fetch_as_sam(self, which, win):
+        """The six outputs as SAM text: gathered on the device, else the wanted records printed there, else packed for the
+        host printer.  -> the profile's counter for the way the window went."""
+        bamdev, n = self.bamdev, win.block.n
+        if self.bam_bins_on_device:
+            # the six outputs themselves, gathered on the device: what comes back is what the sinks get
+            bins = bamdev.fetch_bins(which, n, self.paired, self.sink_mask)
+            if bins[0] == 0:
+                win.bins = bins
+                self.prof.add("bam_windows_device_bins", 1)
+                return "bam_windows_device_text"
+        if self.bam_text_on_device:
+            lines = bamdev.fetch_text(which, n, self.paired, self.sink_mask)
+            if lines[0] == 0:
+                win.lines = lines
+                return "bam_windows_device_text"
+            # (status 1: a binary64 field -- f and B:f are printed on the device since round 6 --, 2: more text than the
+            # slot's buffers hold: the host prints THIS window; the next one is offered to the device again)
+        win.packed = bamdev.fetch_wanted(which, n, self.paired, self.sink_mask)
+        return "bam_windows_host_text"
+
+    def _finish_bam_window(self, win):
+        """settle's first step for a window of the GPU BAM path: the records' SAM text, printed by the host threads when the
+        block is settled -- in the main thread, while the helper thread has the GPU inflate and strip the NEXT window (printing
+        in parse_next instead would put the two in a row)."""
+        prof, blk = self.prof, win.block
+        which = blk.slot
+        with prof("parse"):
+            t_w = time.perf_counter()
+            self.bamdev.raw_wait(which)                              # the copy of the window ran beside the kernels and the next window's inflate
+            prof.add("bam_wait_raw", time.perf_counter() - t_w)
+            if win.bins is not None:                                 # gathered on the device: the outputs themselves are here
+                return
+            if self.out_bam and win.packed is not None:              # BAM outputs: the wanted records, packed -- the host assembles
+                raw_addr, places, nbytes = win.packed
+                win.bam_src = ([_ffi._host_view(raw_addr[f], max(nbytes[f], 1), np.uint8) for f in (0, 1)], list(places))
+                return
+            if self.out_bam:                                         # ... or the whole windows and the table of the yielded records
+                win.bam_src = (self._inflated(blk), [_ffi._host_view(blk.rec_off_addr[f], max(blk.n, 1), np.uint32) for f in (0, 1)])
+            if win.lines is not None:                                # printed on the device: the text and its line table are here
+                _st, text, loff, llen = win.lines
+                win.raws[0], win.raws[1] = text[0], text[1]
+                blk.set_text(list(loff), list(llen))
+                return
+            loffs, llens = [], []
+            # A unit's lines come from ONE file (primary bins: file 1, secondary bins: file 2, unresolved: both; :423-448),
+            # and a bin without a sink prints nothing: with the bins known on the device, only those records came back
+            # (packed; their table says where each went), and only those are printed
+            wanted = [None, None]
+            raw_addr, off_addr = blk.raw_addr, blk.rec_off_addr
+            if win.packed is not None:
+                raw_addr, places, _bytes = win.packed
+                off_addr = [places[0].ctypes.data if blk.n else 0, places[1].ctypes.data if blk.n else 0]
+                wanted = [(places[f] != 0xFFFFFFFF).view(np.uint8) for f in (0, 1)]
+            t_p = time.perf_counter()
+            for f in (0, 1):
+                text, loff, llen, _got = self._print_records(which, f, raw_addr[f], off_addr[f], blk.n, sparse=True,
+                                                             wanted=wanted[f])
+                win.raws[f] = text
+                loffs.append(loff); llens.append(llen)
+            prof.add("bam_print", time.perf_counter() - t_p)
+            blk.set_text(loffs, llens)
+
+    # ---- classify and write one window
+
+    def settle(self, win, parser, pending):
+        """Classify one parsed block and hand its units to the sinks.  Returns the input error to raise once the
+        units in front of it have been written (one found while resolving the stripper's exceptions comes first)."""
+        if win.finish is not None:
+            win.finish(win)                                      # GPU BAM path: print the records' text now
+        block, raws, pos = win.block, win.raws, win.pos
+        n = block.n
+        on_device = isinstance(block, (_ffi.StrippedBlock, _ffi.BamDevBlock))
+        flagged, patches, bad, err = self._resolve(win)
+        if err is not None:
+            n, pending = bad, err                                # units closing at index >= bad are not reached
+        ready = win.bins if (not flagged and err is None) else None
+        if on_device and block.n and ready is None and block.tables is not None:
+            parser.adopt_lines(raws[0], pos[0], raws[1], pos[1], block.n, block.tables)
+        if n:
+            with self.prof("classify"):     # one fused pass: category bytes, counts and the six bin lists
+                code, idx, off, counts = self._classify(win, n, patches, on_device)
+            limit, state_error = self._fell_through(win, code, idx, off, ready)
+            self._write_bins(win, parser, code, idx, off, limit, ready)
+            if state_error is not None:
+                raise state_error
+            _add_counts(self.totals, self.key_order, self.paired, code, counts)
+        return pending
+
+    def _resolve(self, win):
+        """The values the stripper flagged, read by the plugin -> (any flagged, patches, bad, err) as _resolve_exceptions."""
+        block = win.block
+        exc = block.exc
+        if not exc:
+            return False, {}, None, None
+        n = block.n
+        flags = np.unpackbits(block.unit_bits.view(np.uint8), bitorder="little")[:n].astype(bool)
+        if self.paired:
+            needed = flags.copy()
+            needed[:-1] |= flags[1:]
+        else:
+            needed = np.ones(n, dtype=bool)
+        return (True,) + tuple(_resolve_exceptions(block, win.raws, win.pos, needed, self.tag_func, self.cigar_mode))
+
+    def _classify(self, win, n, patches, on_device):
+        """Who classifies the first n records: done already, the front end that holds the columns, or the context from the host's."""
+        block = win.block
+        if on_device and not patches and n == block.n and win.classified is not None:
+            return win.classified                                # classified right behind the strip kernels (GPU BAM path)
+        if on_device and not patches:                            # the columns never left the device
+            return block.stripper.classify(block.slot, self.mode, n, _floor_min_score(self.min_score))
+        return _classify_parsed(self.ctx, self.mode, block, n, patches, self.cigar_mode, self.min_score)
+
+    def _fell_through(self, win, code, idx, off, ready):
+        """A unit that fell through every branch (ref :289) -> (its index: units from there on are not written, the error the
+        reference raises there); (None, None) for a window without one."""
+        if int(off[7]) == int(off[6]):
+            return None, None
+        if ready is not None:                                    # (state 6 needs a NaN: not on the int32 columns of this path)
+            raise RuntimeError("a unit fell through every branch on the GPU BAM path")
+        limit = int(idx[int(off[6]):int(off[7])].min())
+        j = limit - 1 if (self.paired and (int(code[limit]) >> 3) > 5) else limit    # the mate that fell through, as _run()
+        shown = []
+        for f in (0, 1):                                         # the values the reference would print: the plugin's own
+            fields = _fields_of(win.raws[f], win.block, f, j, win.pos[f])
+            shown += [self.tag_func(fields, tag="AS"), self.tag_func(fields, tag="XS")]
+        return limit, RuntimeError("Error in processing logic with values {0} ".format(tuple(shown)))
+
+    def _write_bins(self, win, parser, code, idx, off, limit, ready):
+        """The units of one window to the sinks, bin by bin; `limit`: only the units in front of that index."""
+        prof, paired = self.prof, self.paired
+        for b in range(6):
+            sink = self.sinks[b]
+            if not sink:
+                continue
+            if ready is not None:
+                # the outputs were gathered on the device (xm_bamdev_fetch_bins / xm_strip_fetch_bins): six byte ranges, written
+                # as they stand (into a regular file's pages by the writer's threads, else through the sink)
+                _st, text, boff = ready
+                if boff[b + 1] > boff[b]:
+                    piece = text[boff[b]:boff[b + 1]]
+                    if self.out_bam:                             # what crossed the link is what is written: the framed members
+                        prof.add("bam_out_bytes", int(boff[b + 1] - boff[b]))
+                    with prof("emit"):
+                        done = _emit_into_file(parser, paired, b, None, sink, self.ahead, self.ahead_pool, ready=piece)
+                    if not done:
+                        with prof("write"):
+                            _write_bytes(sink, piece)
+                continue
+            if not (self.out_bam or self.distinct):              # shared sinks: unit by unit, below
+                continue
+            seg = idx[int(off[b]):int(off[b + 1])]
+            if limit is not None:
+                seg = seg[seg < limit]
+            if self.out_bam:
+                # BAM outputs of a window the device did not gather: the same records through the host assembler
+                with prof("emit"):
+                    data = _bgzf_frame(_bam_records_of(seg, paired, b, win.bam_src[0], win.bam_src[1], self.ref_shift), 1)
+                prof.add("bam_out_bytes", len(data))
+                with prof("write"):
+                    _write_bytes(sink, data)
+            else:
+                with prof("emit"):
+                    done = _emit_into_file(parser, paired, b, seg, sink, self.ahead, self.ahead_pool)
+                    text = None if done else parser.emit(paired, b, seg, reuse=True)
+                with prof("write"):
+                    _write_bytes(sink, text)
+        if not self.distinct:
+            _emit_shared(parser, paired, code, idx, off, self.sinks, limit)
+
+
+def _run_files(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_threads=0, bam=False, starts=None, out_bam=False,
+               bam_compress=False):
+    """The three main loops on two SAM (or BAM) *files*: same results as _run(mode, getReadPairs(...)), with the
+    text work done by the C++ stripper / writer.  Falls back to the Python reader when the input is not ASCII.
+    out_bam: the sinks (_BamSink, one per bin) get the units' alignment records as BGZF members instead of their SAM text -- the
+    windows the device takes gathered and framed there (xm_bamdev_fetch_bins_bam; bam_compress: gathered, deflated and framed there,
+    xm_bamdev_fetch_bins_bamz), the others assembled by _bam_records_of."""
+    run = _FileRun(mode, path1, path2, sinks, min_score, tag_func, skip_repeated, n_threads, bam, starts, out_bam, bam_compress)
+    try:
+        return run.run()
+    finally:
+        run.close()
 
 
 def _emit_shared(parser, paired, code, idx, off, sinks, limit):
@@ -2209,9 +2358,7 @@ def _finish_in_python(mode, path1, path2, pos, sinks, min_score, tag_func, skip_
         pairs = _lockstep(lambda: f1.readline().strip("\n").split(), lambda: f2.readline().strip("\n").split(),
                           skip_repeated)                          # a plain generator: _run must not come back here
         rest = _run(mode, pairs, sinks, min_score, tag_func)
-    ordered = Counter()
-    for key in key_order:
-        ordered[key] = totals[key]
+    ordered = _ordered_counts(totals, key_order)
     for key, val in rest.items():
         ordered[key] += val
     return ordered
