@@ -68,9 +68,11 @@ class Mappability(dict):
         for chrom in self:
             track = np.asarray(self[chrom], dtype=np.float64)
             values = ctx.mate_correlate(track, density).tolist()
-            if len(values) != len(paired[chrom]):          # the reference would raise IndexError while assigning
+            # the reference assigns element by element into [0] * size: a longer track raises IndexError on the way, a
+            # shorter one leaves the integer zeros behind it
+            if len(values) > len(paired[chrom]):
                 raise IndexError("list assignment index out of range")
-            paired[chrom] = values
+            paired[chrom][:len(values)] = values
         return paired
 
 
