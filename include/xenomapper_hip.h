@@ -221,7 +221,9 @@ int xm_classify_cigar_dev(xm_ctx *ctx, void *stream, int mode, uint64_t n_record
                           const uint64_t *unit_bits, int32_t min_score_floor, uint8_t *code_out,
                           uint32_t *range_flag);
 
-/* range_flag: one device uint32, set non-zero when a score left int32 (may be NULL). */
+/* range_flag: one device uint32, set non-zero when a score left int32 (may be NULL); never cleared by the library.  A score
+ * of INT32_MIN or below, or above INT32_MAX, has left it: INT32_MIN itself is XM_ABSENT.  Such a score is clamped to
+ * INT32_MIN + 1 / INT32_MAX, and every output holds what the clamped score gives (all xm_*cigar*_dev calls alike). */
 int xm_cigar_scores_dev(xm_ctx *ctx, void *stream, uint64_t n_records, const int32_t *nm,
                         const uint32_t *cig_off, const uint32_t *cig_oplen, int32_t *as_out,
                         uint32_t *range_flag);

@@ -22,6 +22,7 @@ Vectors:
   G9  the command line as a child process: stdout, stderr, exit code, output files
   G10 the companion tool's command line as a child process
   G11 the rows of tests/test_oracle_vs_reference.py: its property test's draws, the companion tool's helpers
+  G12 get_cigarbased_AS_tag on every record kind of tests/cigar_shapes.py that a SAM line can express: kind -> score
 """
 import gzip
 import hashlib
@@ -678,6 +679,21 @@ def g11(n_cases=300):
     return {"cases": cases, "mappability": rows}
 
 
+# ------------------------------------------------------------------ G12
+def g12():
+    """The reference's score of every record kind of the CIGAR catalogue (tests/cigar_shapes.py) that can be written as a
+    SAM line: op codes 0..8, NM as NM:i:, a line without NM for the absent case.  Names and integers only."""
+    from tests import cigar_shapes
+    kinds = {}
+    for kind in sorted(cigar_shapes.KINDS):
+        if kind in cigar_shapes.BINARY_ONLY:                         # op codes 9..15: only the binary columns hold them
+            continue
+        val = ref.get_cigarbased_AS_tag(cigar_shapes.sam_fields(kind), tag="AS")
+        assert val == NEG or isinstance(val, int)
+        kinds[kind] = num(val)
+    return {"kinds": kinds, "excluded": sorted(cigar_shapes.BINARY_ONLY)}
+
+
 def header_golden():
     """process_headers on the PE fixtures (tests/test_xenomapper.py:29-54): full texts."""
     data_dir = os.path.join(REF_ROOT, "xenomapper", "tests", "data")
@@ -693,7 +709,8 @@ def main():
     payload = {"g1_mapping_state.json": g1(), "g2_tag_parsers.json": g2(), "g3_end_to_end.json": g3(),
                "g4_headers.json": header_golden(), "g5_errors.json": g5(), "g6_mappability.json": g6(),
                "g7_random_corpus.json": g7(), "g8_large_runs.json": g8(),
-               "g9_cli.json": g9(), "g10_mappability_cli.json": g10(), "g11_differential.json.gz": g11()}
+               "g9_cli.json": g9(), "g10_mappability_cli.json": g10(), "g11_differential.json.gz": g11(),
+               "g12_cigar_kinds.json": g12()}
     for name, obj in payload.items():
         with open(os.path.join(GOLDEN, name), "wb") as raw:
             text = json.dumps(obj, indent=None, separators=(",", ":"), sort_keys=True) + "\n"
