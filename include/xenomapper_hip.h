@@ -201,9 +201,29 @@ int xm_pinned_bytes(uint64_t *allocated, uint64_t *registered, uint64_t *peak);
 /*
  * All pointers are device memory of the context's device; `stream` is a hipStream_t passed
  * as void* (NULL = the default stream).  Nothing is synchronised or allocated: the calls
- * only enqueue work (graph-capturable).  Column base pointers must be 16-byte aligned and
- * code 4-byte aligned (any hipMalloc / torch allocation is).  n_records <= XM_MAX_RECORDS.  The calling
- * thread's current HIP device must be the context's device (XM_ERR_INVALID_ARG otherwise).
+ * only enqueue work (graph-capturable).  n_records <= XM_MAX_RECORDS.  The calling thread's
+ * current HIP device must be the context's device (XM_ERR_INVALID_ARG otherwise).
+ *
+ * Where a buffer may lie (any hipMalloc / torch allocation satisfies all of it; a pointer INTO an allocation must
+ * be placed accordingly).  One rule per kind of parameter, the same in every call that takes it:
+ *   int32 / uint32 score columns read 4 records a lane   as1 xs1 as2 xs2, nm* xs*, the CSR cig_off* of the
+ *       (16-byte loads)                                  xm_classify*_cigar_dev calls, c0..c3          16 bytes
+ *   binary64 score columns (32-byte loads)               as1 xs1 as2 xs2 of every *_f64_dev call       32 bytes
+ *   unit_bits (32-byte scalar loads of 64-bit words)                                                    8 bytes
+ *   the 64-bit outputs                                   bin_offsets, n_out, counts                     8 bytes
+ *   code / code_out                                      xm_classify_dev, _f64_dev, _cigar_dev          4 bytes
+ *                                                        every compacting call (*_compact*, *_place*)  16 bytes
+ *   bins4, runs16, gran_counts                                                                         16 bytes
+ *   index lists                                          idx_out, the six idx_out[b], idx_state6        4 bytes
+ *       (16-byte alignment lets the single-end form store whole 16-byte groups; any 4-byte placement is correct)
+ *   everything read or written a dword at a time         cig_oplen*, cig_cnt*, cig_tile*, range_flag, and all of
+ *                                                        xm_cigar_scores_dev (nm, cig_off, cig_oplen, as_out)  4 bytes
+ *   xm_mate_correlate_dev                                track, density, out                            8 bytes
+ *   xm_stream_probe_dev                                  out                                            2 bytes
+ * A pointer that breaks its rule, a NULL where none is allowed, a mode outside the three and n_records >
+ * XM_MAX_RECORDS are refused with XM_ERR_INVALID_ARG before anything is enqueued: no output byte and nothing of the
+ * context's workspace is touched, and no pointer has been dereferenced.  With n_records == 0 the columns may be NULL.
+ * tests/abi_placements.py is this paragraph as a table, one row per call; tests/test_abi_placements_*.py run it.
  */
 #define XM_MAX_RECORDS 0xFFFFF000ull
 
@@ -221,17 +241,20 @@ int xm_classify_cigar_dev(xm_ctx *ctx, void *stream, int mode, uint64_t n_record
                           const uint64_t *unit_bits, int32_t min_score_floor, uint8_t *code_out,
                           uint32_t *range_flag);
 
-/* range_flag: one device uint32, set non-zero when a score left int32 (may be NULL); never cleared by the library.  A score
+/* range_flag: one device uint32 (4-byte aligned), set non-zero when a score left int32 (may be NULL); never cleared by the library.  A score
  * of INT32_MIN or below, or above INT32_MAX, has left it: INT32_MIN itself is XM_ABSENT.  Such a score is clamped to
  * INT32_MIN + 1 / INT32_MAX, and every output holds what the clamped score gives (all xm_*cigar*_dev calls alike). */
 int xm_cigar_scores_dev(xm_ctx *ctx, void *stream, uint64_t n_records, const int32_t *nm,
                         const uint32_t *cig_off, const uint32_t *cig_oplen, int32_t *as_out,
                         uint32_t *range_flag);
 
+/* xm_mate_correlate on device memory: track[n], density[m], out[n], each 8-byte aligned; n <= 2^40, m < 2^32; density may be
+ * NULL when m == 0. */
 int xm_mate_correlate_dev(xm_ctx *ctx, void *stream, uint64_t n, const double *track, uint64_t m,
                           const double *density, double *out);
 
-/* bin_offsets: 8 device uint64; counts: 64 device uint64 (both overwritten).
+/* bin_offsets: 8 device uint64; counts: 64 device uint64 (both overwritten, both 8-byte aligned; with n_records == 0 both
+ * are zeroed and nothing else is looked at).  code 16-byte aligned, idx_out 4-byte aligned.
  * The compaction workspace (per-granule counts and offsets, the count replicas, the part totals) belongs to the context:
  * ONE xm_compact_dev / xm_classify_compact*_dev / xm_classify_place*_dev call can be in flight per context at a time.
  * Calls on one stream are ordered anyway; a call issued on another stream than the previous one is put behind
@@ -320,7 +343,7 @@ int xm_classify_compact_cigar_packed_dev(xm_ctx *ctx, void *stream, int mode, ui
  * The fused main loop with the six-list output contract of SURVEY 8b (4) (see xm_classify_place above) on device-resident
  * columns: idx_out is a HOST array of six DEVICE pointers (4-byte aligned; 16-byte alignment lets the single-end form
  * store 16 bytes at a time), each list with room for list_capacity entries; n_out = 8 device uint64 (six list lengths,
- * units holding state 6, all units), counts = 64 device uint64.  code_out / bins4 as for xm_classify_compact_dev (at
+ * units holding state 6, all units), counts = 64 device uint64, both 8-byte aligned.  code_out / bins4 as for xm_classify_compact_dev (at
  * least one).  Same three launches and the same one-in-flight rule as xm_classify_compact_dev: the classify kernel
  * counts per bin and granule, the scan gives every granule its place in each bin, and the scatter writes bin b's units
  * to list b -- a unit's place no longer depends on the totals of the bins in front of its own.
@@ -365,7 +388,8 @@ int xm_classify_place_cigar_packed_dev(xm_ctx *ctx, void *stream, int mode, uint
  * in a FLAT list needs the totals of all granules in front of it -- a prefix over the whole input, i.e. the scan and the
  * second pass of xm_classify_compact_dev (a look-back inside one launch lost by 3-7x in round 4) -- while its
  * place inside its own granule's run needs nothing from outside the workgroup.  Same one-in-flight rule (the count
- * replicas belong to the context).  Columns 16-byte aligned (binary64: 32), runs16 and gran_counts 16-byte aligned.
+ * replicas belong to the context).  Columns 16-byte aligned (binary64: 32), runs16 and gran_counts 16-byte aligned, unit_bits,
+ * n_out and counts 8-byte aligned.
  */
 #define XM_RUNS_GRAN 2048u
 #define XM_RUNS_GRANULES(n_records) (((uint64_t)(n_records) + XM_RUNS_GRAN - 1u) / XM_RUNS_GRAN)
@@ -409,7 +433,7 @@ int xm_workspace_is_clean(xm_ctx *ctx, int *clean);
  * Measurement aid ("measure an on-box streaming-copy ceiling alongside" the 8 TB/s specification): the classify
  * kernel's memory shape without its arithmetic -- reads 16 bytes per record from four int32 columns (n_records rounded down
  * to a multiple of 4), writes XM_BINS4_BYTES(n_records) bytes at most to `out` (the compact stream's size).  The values
- * written mean nothing.  Timed by the caller (events on `stream`).
+ * written mean nothing.  Timed by the caller (events on `stream`).  Columns 16-byte aligned, out 2-byte aligned.
  */
 int xm_stream_probe_dev(xm_ctx *ctx, void *stream, uint64_t n_records,
                         const int32_t *c0, const int32_t *c1, const int32_t *c2, const int32_t *c3, uint8_t *out);

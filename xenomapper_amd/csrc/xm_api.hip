@@ -153,6 +153,15 @@ bool wrong_device(const xm_ctx *ctx)
     return hipGetDevice(&cur) != hipSuccess || cur != ctx->device;
 }
 
+// Placement contract of the device-resident entry points (include/xenomapper_hip.h; the table of it is tests/abi_placements.py):
+// true when some pointer is not aligned to mask + 1 bytes.  NULL passes -- where NULL is not allowed it is tested by name.
+// Every such test comes before anything is enqueued and before order_workspace: a refused call leaves nothing behind.
+template <typename... P>
+bool misaligned(uintptr_t mask, P... p) { return ((... | (uintptr_t)p) & mask) != 0; }
+
+// the two 64-bit outputs every counting call has (bin_offsets / n_out, counts): given, and 8-byte aligned
+bool bad_totals(const uint64_t *offsets, const uint64_t *counts) { return !offsets || !counts || misaligned(7u, offsets, counts); }
+
 void reset_count_state(xm_ctx *ctx, hipStream_t st)
 {
     (void)hipMemsetAsync(ctx->d_counts_rep, 0, COUNTS_REP_BYTES, st);
@@ -338,8 +347,7 @@ int xm_classify_dev(xm_ctx *ctx, void *stream, int mode, uint64_t n,
     if (!ctx || bad_mode(mode) || n > XM_MAX_RECORDS || wrong_device(ctx)) return XM_ERR_INVALID_ARG;
     if (n == 0) return XM_OK;
     if (!as1 || !xs1 || !as2 || !xs2 || !unit_bits || !code_out) return XM_ERR_INVALID_ARG;
-    if ((((uintptr_t)as1 | (uintptr_t)xs1 | (uintptr_t)as2 | (uintptr_t)xs2) & 15u) || ((uintptr_t)code_out & 3u))
-        return XM_ERR_INVALID_ARG;
+    if (misaligned(15u, as1, xs1, as2, xs2) || misaligned(7u, unit_bits) || misaligned(3u, code_out)) return XM_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     {
         Span span(ctx, st, XM_K_CLASSIFY);
@@ -355,8 +363,7 @@ int xm_classify_f64_dev(xm_ctx *ctx, void *stream, int mode, uint64_t n,
     if (!ctx || bad_mode(mode) || n > XM_MAX_RECORDS || wrong_device(ctx)) return XM_ERR_INVALID_ARG;
     if (n == 0) return XM_OK;
     if (!as1 || !xs1 || !as2 || !xs2 || !unit_bits || !code_out) return XM_ERR_INVALID_ARG;
-    if ((((uintptr_t)as1 | (uintptr_t)xs1 | (uintptr_t)as2 | (uintptr_t)xs2) & 31u) || ((uintptr_t)code_out & 3u))
-        return XM_ERR_INVALID_ARG;
+    if (misaligned(31u, as1, xs1, as2, xs2) || misaligned(7u, unit_bits) || misaligned(3u, code_out)) return XM_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     {
         Span span(ctx, st, XM_K_CLASSIFY);
@@ -374,8 +381,8 @@ int xm_classify_cigar_dev(xm_ctx *ctx, void *stream, int mode, uint64_t n,
     if (n == 0) return XM_OK;
     if (!nm1 || !off1 || !ops1 || !xs1 || !nm2 || !off2 || !ops2 || !xs2 || !unit_bits || !code_out)
         return XM_ERR_INVALID_ARG;
-    if ((((uintptr_t)nm1 | (uintptr_t)off1 | (uintptr_t)xs1 | (uintptr_t)nm2 | (uintptr_t)off2 | (uintptr_t)xs2) & 15u) ||
-        ((uintptr_t)code_out & 3u))
+    if (misaligned(15u, nm1, off1, xs1, nm2, off2, xs2) || misaligned(7u, unit_bits) ||
+        misaligned(3u, ops1, ops2, code_out, range_flag))
         return XM_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     {
@@ -393,6 +400,8 @@ int xm_cigar_scores_dev(xm_ctx *ctx, void *stream, uint64_t n, const int32_t *nm
     if (!ctx || n > XM_MAX_RECORDS || wrong_device(ctx)) return XM_ERR_INVALID_ARG;
     if (n == 0) return XM_OK;
     if (!nm || !cig_off || !cig_oplen || !as_out) return XM_ERR_INVALID_ARG;
+    // cigar_kernel reads and writes one dword per lane (no vector access): element alignment is all it needs
+    if (misaligned(3u, nm, cig_off, cig_oplen, as_out, range_flag)) return XM_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     {
         Span span(ctx, st, XM_K_CIGAR);
@@ -448,11 +457,11 @@ int xm_compact_dev(xm_ctx *ctx, void *stream, int mode, uint64_t n, const uint8_
                    uint32_t *idx_out, uint64_t *bin_offsets, uint64_t *counts)
 {
     if (!ctx || bad_mode(mode) || n > XM_MAX_RECORDS || wrong_device(ctx)) return XM_ERR_INVALID_ARG;
-    if (!bin_offsets || !counts) return XM_ERR_INVALID_ARG;
+    if (bad_totals(bin_offsets, counts)) return XM_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return empty_compact(ctx, st, bin_offsets, counts);
     // d_counts_rep is all zero here: zeroed at context creation and by every K2b after it has summed it
-    if (!code || !idx_out || ((uintptr_t)code & 15u)) return XM_ERR_INVALID_ARG;
+    if (!code || !idx_out || misaligned(15u, code) || misaligned(3u, idx_out)) return XM_ERR_INVALID_ARG;
     const xm::CountPlan cp = count_plan(ctx, n);
     int rc;
     if ((rc = order_workspace(ctx, st)) != XM_OK) return rc;
@@ -472,11 +481,11 @@ int xm_classify_compact_dev(xm_ctx *ctx, void *stream, int mode, uint64_t n,
                             uint32_t *idx_out, uint64_t *bin_offsets, uint64_t *counts)
 {
     if (!ctx || bad_mode(mode) || n > XM_MAX_RECORDS || wrong_device(ctx)) return XM_ERR_INVALID_ARG;
-    if (!bin_offsets || !counts) return XM_ERR_INVALID_ARG;
+    if (bad_totals(bin_offsets, counts)) return XM_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return empty_compact(ctx, st, bin_offsets, counts);
     if (!as1 || !xs1 || !as2 || !xs2 || !unit_bits || (!code_out && !bins4) || !idx_out) return XM_ERR_INVALID_ARG;
-    if ((((uintptr_t)as1 | (uintptr_t)xs1 | (uintptr_t)as2 | (uintptr_t)xs2 | (uintptr_t)code_out | (uintptr_t)bins4) & 15u))
+    if (misaligned(15u, as1, xs1, as2, xs2, code_out, bins4) || misaligned(7u, unit_bits) || misaligned(3u, idx_out))
         return XM_ERR_INVALID_ARG;
     xm::CountPlan cp = count_plan(ctx, n);
     cp.bins4 = bins4;
@@ -496,11 +505,11 @@ int xm_classify_compact_f64_dev(xm_ctx *ctx, void *stream, int mode, uint64_t n,
                                 uint32_t *idx_out, uint64_t *bin_offsets, uint64_t *counts)
 {
     if (!ctx || bad_mode(mode) || n > XM_MAX_RECORDS || wrong_device(ctx)) return XM_ERR_INVALID_ARG;
-    if (!bin_offsets || !counts) return XM_ERR_INVALID_ARG;
+    if (bad_totals(bin_offsets, counts)) return XM_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return empty_compact(ctx, st, bin_offsets, counts);
     if (!as1 || !xs1 || !as2 || !xs2 || !unit_bits || (!code_out && !bins4) || !idx_out) return XM_ERR_INVALID_ARG;
-    if ((((uintptr_t)as1 | (uintptr_t)xs1 | (uintptr_t)as2 | (uintptr_t)xs2) & 31u) || (((uintptr_t)code_out | (uintptr_t)bins4) & 15u))
+    if (misaligned(31u, as1, xs1, as2, xs2) || misaligned(15u, code_out, bins4) || misaligned(7u, unit_bits) || misaligned(3u, idx_out))
         return XM_ERR_INVALID_ARG;
     xm::CountPlan cp = count_plan(ctx, n);
     cp.bins4 = bins4;
@@ -521,13 +530,13 @@ int xm_classify_compact_cigar_dev(xm_ctx *ctx, void *stream, int mode, uint64_t 
                                   uint32_t *range_flag, uint32_t *idx_out, uint64_t *bin_offsets, uint64_t *counts)
 {
     if (!ctx || bad_mode(mode) || n > XM_MAX_RECORDS || wrong_device(ctx)) return XM_ERR_INVALID_ARG;
-    if (!bin_offsets || !counts) return XM_ERR_INVALID_ARG;
+    if (bad_totals(bin_offsets, counts)) return XM_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return empty_compact(ctx, st, bin_offsets, counts);
     if (!nm1 || !off1 || !ops1 || !xs1 || !nm2 || !off2 || !ops2 || !xs2 || !unit_bits || !code_out || !idx_out)
         return XM_ERR_INVALID_ARG;
-    if ((((uintptr_t)nm1 | (uintptr_t)off1 | (uintptr_t)xs1 | (uintptr_t)nm2 | (uintptr_t)off2 | (uintptr_t)xs2 |
-          (uintptr_t)code_out) & 15u))
+    if (misaligned(15u, nm1, off1, xs1, nm2, off2, xs2, code_out) || misaligned(7u, unit_bits) ||
+        misaligned(3u, ops1, ops2, range_flag, idx_out))
         return XM_ERR_INVALID_ARG;
     // K1c (CSR columns) does not count (it measured slower with the counting epilogue than with a separate histogram
     // pass): classify, then the stand-alone compaction on the category bytes it wrote.  The counting form of this path
@@ -551,14 +560,14 @@ int xm_classify_compact_cigar_packed_dev(xm_ctx *ctx, void *stream, int mode, ui
                                          uint32_t *range_flag, uint32_t *idx_out, uint64_t *bin_offsets, uint64_t *counts)
 {
     if (!ctx || bad_mode(mode) || n > XM_MAX_RECORDS || wrong_device(ctx)) return XM_ERR_INVALID_ARG;
-    if (!bin_offsets || !counts) return XM_ERR_INVALID_ARG;
+    if (bad_totals(bin_offsets, counts)) return XM_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return empty_compact(ctx, st, bin_offsets, counts);
     if (!nm1 || !cnt1 || !tile1 || !ops1 || !xs1 || !nm2 || !cnt2 || !tile2 || !ops2 || !xs2 || !unit_bits ||
         (!code_out && !bins4) || !idx_out)
         return XM_ERR_INVALID_ARG;
-    if ((((uintptr_t)nm1 | (uintptr_t)xs1 | (uintptr_t)nm2 | (uintptr_t)xs2 | (uintptr_t)code_out | (uintptr_t)bins4) & 15u) ||
-        (((uintptr_t)cnt1 | (uintptr_t)cnt2 | (uintptr_t)tile1 | (uintptr_t)tile2 | (uintptr_t)ops1 | (uintptr_t)ops2) & 3u))
+    if (misaligned(15u, nm1, xs1, nm2, xs2, code_out, bins4) || misaligned(7u, unit_bits) ||
+        misaligned(3u, cnt1, cnt2, tile1, tile2, ops1, ops2, range_flag, idx_out))
         return XM_ERR_INVALID_ARG;
     xm::CountPlan cp = count_plan(ctx, n);
     cp.bins4 = bins4;
@@ -579,10 +588,10 @@ static int list_out(uint32_t *const idx_out[6], uint32_t *idx_state6, uint64_t l
 {
     if (!idx_out) return XM_ERR_INVALID_ARG;
     for (int b = 0; b < 6; ++b) {
-        if (!idx_out[b] || ((uintptr_t)idx_out[b] & 3u)) return XM_ERR_INVALID_ARG;
+        if (!idx_out[b] || misaligned(3u, idx_out[b])) return XM_ERR_INVALID_ARG;
         lo.p[b] = idx_out[b];
     }
-    if ((uintptr_t)idx_state6 & 3u) return XM_ERR_INVALID_ARG;
+    if (misaligned(3u, idx_state6)) return XM_ERR_INVALID_ARG;
     lo.p[6] = idx_state6;
     lo.cap = list_capacity > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)list_capacity;
     return XM_OK;
@@ -640,15 +649,14 @@ int xm_classify_place_dev(xm_ctx *ctx, void *stream, int mode, uint64_t n,
                           uint32_t *const idx_out[6], uint64_t list_capacity, uint64_t *n_out, uint64_t *counts)
 {
     if (!ctx || bad_mode(mode) || n > XM_MAX_RECORDS || wrong_device(ctx)) return XM_ERR_INVALID_ARG;
-    if (!n_out || !counts) return XM_ERR_INVALID_ARG;
+    if (bad_totals(n_out, counts)) return XM_ERR_INVALID_ARG;
     xm::ListOut lo;
     int rc;
     if ((rc = list_out(idx_out, nullptr, list_capacity, lo)) != XM_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return empty_compact(ctx, st, n_out, counts);
     if (!as1 || !xs1 || !as2 || !xs2 || !unit_bits || (!code_out && !bins4)) return XM_ERR_INVALID_ARG;
-    if ((((uintptr_t)as1 | (uintptr_t)xs1 | (uintptr_t)as2 | (uintptr_t)xs2 | (uintptr_t)code_out | (uintptr_t)bins4) & 15u))
-        return XM_ERR_INVALID_ARG;
+    if (misaligned(15u, as1, xs1, as2, xs2, code_out, bins4) || misaligned(7u, unit_bits)) return XM_ERR_INVALID_ARG;
     xm::CountPlan cp = count_plan(ctx, n);
     cp.bins4 = bins4;
     if ((rc = order_workspace(ctx, st)) != XM_OK) return rc;
@@ -664,15 +672,14 @@ int xm_classify_place_f64_dev(xm_ctx *ctx, void *stream, int mode, uint64_t n,
                               uint64_t *n_out, uint64_t *counts)
 {
     if (!ctx || bad_mode(mode) || n > XM_MAX_RECORDS || wrong_device(ctx)) return XM_ERR_INVALID_ARG;
-    if (!n_out || !counts) return XM_ERR_INVALID_ARG;
+    if (bad_totals(n_out, counts)) return XM_ERR_INVALID_ARG;
     xm::ListOut lo;
     int rc;
     if ((rc = list_out(idx_out, idx_state6, list_capacity, lo)) != XM_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return empty_compact(ctx, st, n_out, counts);
     if (!as1 || !xs1 || !as2 || !xs2 || !unit_bits || (!code_out && !bins4)) return XM_ERR_INVALID_ARG;
-    if ((((uintptr_t)as1 | (uintptr_t)xs1 | (uintptr_t)as2 | (uintptr_t)xs2) & 31u) || (((uintptr_t)code_out | (uintptr_t)bins4) & 15u))
-        return XM_ERR_INVALID_ARG;
+    if (misaligned(31u, as1, xs1, as2, xs2) || misaligned(15u, code_out, bins4) || misaligned(7u, unit_bits)) return XM_ERR_INVALID_ARG;
     xm::CountPlan cp = count_plan(ctx, n);
     cp.bins4 = bins4;
     if ((rc = order_workspace(ctx, st)) != XM_OK) return rc;
@@ -691,7 +698,7 @@ int xm_classify_place_cigar_packed_dev(xm_ctx *ctx, void *stream, int mode, uint
                                        uint64_t *n_out, uint64_t *counts)
 {
     if (!ctx || bad_mode(mode) || n > XM_MAX_RECORDS || wrong_device(ctx)) return XM_ERR_INVALID_ARG;
-    if (!n_out || !counts) return XM_ERR_INVALID_ARG;
+    if (bad_totals(n_out, counts)) return XM_ERR_INVALID_ARG;
     xm::ListOut lo;
     int rc;
     if ((rc = list_out(idx_out, nullptr, list_capacity, lo)) != XM_OK) return rc;
@@ -699,8 +706,8 @@ int xm_classify_place_cigar_packed_dev(xm_ctx *ctx, void *stream, int mode, uint
     if (n == 0) return empty_compact(ctx, st, n_out, counts);
     if (!nm1 || !cnt1 || !tile1 || !ops1 || !xs1 || !nm2 || !cnt2 || !tile2 || !ops2 || !xs2 || !unit_bits || (!code_out && !bins4))
         return XM_ERR_INVALID_ARG;
-    if ((((uintptr_t)nm1 | (uintptr_t)xs1 | (uintptr_t)nm2 | (uintptr_t)xs2 | (uintptr_t)code_out | (uintptr_t)bins4) & 15u) ||
-        (((uintptr_t)cnt1 | (uintptr_t)cnt2 | (uintptr_t)tile1 | (uintptr_t)tile2 | (uintptr_t)ops1 | (uintptr_t)ops2) & 3u))
+    if (misaligned(15u, nm1, xs1, nm2, xs2, code_out, bins4) || misaligned(7u, unit_bits) ||
+        misaligned(3u, cnt1, cnt2, tile1, tile2, ops1, ops2, range_flag))
         return XM_ERR_INVALID_ARG;
     xm::CountPlan cp = count_plan(ctx, n);
     cp.bins4 = bins4;
@@ -721,12 +728,11 @@ static int runs_common(xm_ctx *ctx, hipStream_t st, int mode, uint64_t n, size_t
                        int32_t mi, double mf, uint16_t *runs16, uint16_t *gran_counts, uint64_t *n_out, uint64_t *counts)
 {
     if (!ctx || bad_mode(mode) || n > XM_MAX_RECORDS || wrong_device(ctx)) return XM_ERR_INVALID_ARG;
-    if (!n_out || !counts) return XM_ERR_INVALID_ARG;
+    if (bad_totals(n_out, counts)) return XM_ERR_INVALID_ARG;
     if (n == 0) return empty_compact(ctx, st, n_out, counts);
     if (!as1 || !xs1 || !as2 || !xs2 || !unit_bits || !runs16 || !gran_counts) return XM_ERR_INVALID_ARG;
     const uintptr_t col_mask = elem == 8 ? 31u : 15u;
-    if ((((uintptr_t)as1 | (uintptr_t)xs1 | (uintptr_t)as2 | (uintptr_t)xs2) & col_mask) ||
-        (((uintptr_t)runs16 | (uintptr_t)gran_counts) & 15u))
+    if (misaligned(col_mask, as1, xs1, as2, xs2) || misaligned(15u, runs16, gran_counts) || misaligned(7u, unit_bits))
         return XM_ERR_INVALID_ARG;
     const xm::RunsOut ro = {runs16, gran_counts, ctx->d_counts_rep};
     int rc;
@@ -823,7 +829,7 @@ int xm_stream_probe_dev(xm_ctx *ctx, void *stream, uint64_t n,
     if (!ctx || n > XM_MAX_RECORDS || wrong_device(ctx)) return XM_ERR_INVALID_ARG;
     if (n == 0) return XM_OK;
     if (!c0 || !c1 || !c2 || !c3 || !out) return XM_ERR_INVALID_ARG;
-    if ((((uintptr_t)c0 | (uintptr_t)c1 | (uintptr_t)c2 | (uintptr_t)c3) & 15u) || ((uintptr_t)out & 1u)) return XM_ERR_INVALID_ARG;
+    if (misaligned(15u, c0, c1, c2, c3) || misaligned(1u, out)) return XM_ERR_INVALID_ARG;
     xm::launch_stream_probe((hipStream_t)stream, n, c0, c1, c2, c3, out);
     return check_launch(ctx, "stream_probe_kernel");
 }
@@ -834,6 +840,8 @@ int xm_mate_correlate_dev(xm_ctx *ctx, void *stream, uint64_t n, const double *t
     if (!ctx || wrong_device(ctx) || m > 0xFFFFFFFFull || n > (1ull << 40)) return XM_ERR_INVALID_ARG;
     if (n == 0) return XM_OK;
     if (!track || !out || (m && !density)) return XM_ERR_INVALID_ARG;
+    // mate_correlate_kernel reads and writes one binary64 per lane: element alignment (density is read when m != 0 only)
+    if (misaligned(7u, track, out) || (m && misaligned(7u, density))) return XM_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     {
         Span span(ctx, st, XM_K_CORRELATE);
