@@ -34,7 +34,7 @@ int main(int argc, char **argv)
         std::vector<float> t;
         for (int r = 0; r < 12; ++r) {
             CK(hipEventRecord(e0));
-            xm::launch_classify_i32(0, 1, N, col[0], col[1], col[2], col[3], bits, INT32_MIN, code, nullptr);
+            xm::launch_classify<int32_t>(0, 1, N, col[0], col[1], col[2], col[3], bits, INT32_MIN, code, nullptr);
             CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
             float ms; CK(hipEventElapsedTime(&ms, e0, e1)); if (r >= 2) t.push_back(ms);
         }

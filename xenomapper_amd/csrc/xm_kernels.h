@@ -69,22 +69,17 @@ struct RunsOut {
     uint16_t *gran_counts16;    // [n_gran][8]: units per bin of every granule
     uint64_t *counts_rep;       // the context's [XM_COUNT_REPLICAS][64], all zero between calls
 };
-void launch_classify_runs_i32(hipStream_t st, int mode, uint64_t n,
-                              const int32_t *as1, const int32_t *xs1, const int32_t *as2, const int32_t *xs2,
-                              const uint64_t *unit_bits, int32_t m, const RunsOut &ro);
-void launch_classify_runs_f64(hipStream_t st, int mode, uint64_t n,
-                              const double *as1, const double *xs1, const double *as2, const double *xs2,
-                              const uint64_t *unit_bits, double m, const RunsOut &ro);
+// T: int32_t or double, the two element types of the score columns (instantiated in xm_kernels.hip)
+template <typename T>
+void launch_classify_runs(hipStream_t st, int mode, uint64_t n, const T *as1, const T *xs1, const T *as2, const T *xs2,
+                          const uint64_t *unit_bits, T m, const RunsOut &ro);
 // adds up the category_counts replicas (left zeroed) and derives the eight list lengths
 void launch_runs_finish(hipStream_t st, int mode, uint64_t *counts_rep, uint64_t *counts, uint64_t *n_out);
 
-// cp != nullptr: the fused form, the kernel also counts (granule = its workgroup)
-void launch_classify_i32(hipStream_t st, int mode, uint64_t n,
-                         const int32_t *as1, const int32_t *xs1, const int32_t *as2, const int32_t *xs2,
-                         const uint64_t *unit_bits, int32_t m, uint8_t *code, const CountPlan *cp);
-void launch_classify_f64(hipStream_t st, int mode, uint64_t n,
-                         const double *as1, const double *xs1, const double *as2, const double *xs2,
-                         const uint64_t *unit_bits, double m, uint8_t *code, const CountPlan *cp);
+// cp != nullptr: the fused form, the kernel also counts (granule = its workgroup).  T as above.
+template <typename T>
+void launch_classify(hipStream_t st, int mode, uint64_t n, const T *as1, const T *xs1, const T *as2, const T *xs2,
+                     const uint64_t *unit_bits, T m, uint8_t *code, const CountPlan *cp);
 void launch_classify_cigar(hipStream_t st, int mode, uint64_t n,
                            const int32_t *nm1, const uint32_t *off1, const uint32_t *ops1, const int32_t *xs1,
                            const int32_t *nm2, const uint32_t *off2, const uint32_t *ops2, const int32_t *xs2,

@@ -1856,9 +1856,8 @@ static CountSink make_sink(const CountPlan *cp, int mode)
 }
 
 template <typename T>
-static void launch_classify_t(hipStream_t st, int mode, uint64_t n,
-                              const T *as1, const T *xs1, const T *as2, const T *xs2,
-                              const uint64_t *unit_bits, T m, uint8_t *code, const CountPlan *cp)
+void launch_classify(hipStream_t st, int mode, uint64_t n, const T *as1, const T *xs1, const T *as2, const T *xs2,
+                     const uint64_t *unit_bits, T m, uint8_t *code, const CountPlan *cp)
 {
     const uint64_t per_block = (uint64_t)XM_CLASSIFY_BLOCK * 4;
     static_assert(XM_CLASSIFY_BLOCK * 4 == XM_GRAN, "a counting workgroup is a granule: CountPlan's chunk is in both");
@@ -1878,24 +1877,14 @@ static void launch_classify_t(hipStream_t st, int mode, uint64_t n,
 #undef XM_LAUNCH_CLS
 }
 
-void launch_classify_i32(hipStream_t st, int mode, uint64_t n,
-                         const int32_t *as1, const int32_t *xs1, const int32_t *as2, const int32_t *xs2,
-                         const uint64_t *unit_bits, int32_t m, uint8_t *code, const CountPlan *cp)
-{
-    launch_classify_t<int32_t>(st, mode, n, as1, xs1, as2, xs2, unit_bits, m, code, cp);
-}
-
-void launch_classify_f64(hipStream_t st, int mode, uint64_t n,
-                         const double *as1, const double *xs1, const double *as2, const double *xs2,
-                         const uint64_t *unit_bits, double m, uint8_t *code, const CountPlan *cp)
-{
-    launch_classify_t<double>(st, mode, n, as1, xs1, as2, xs2, unit_bits, m, code, cp);
-}
+template void launch_classify<int32_t>(hipStream_t, int, uint64_t, const int32_t *, const int32_t *, const int32_t *, const int32_t *,
+                                       const uint64_t *, int32_t, uint8_t *, const CountPlan *);
+template void launch_classify<double>(hipStream_t, int, uint64_t, const double *, const double *, const double *, const double *,
+                                      const uint64_t *, double, uint8_t *, const CountPlan *);
 
 template <typename T>
-static void launch_classify_runs_t(hipStream_t st, int mode, uint64_t n,
-                                   const T *as1, const T *xs1, const T *as2, const T *xs2,
-                                   const uint64_t *unit_bits, T m, const RunsOut &ro)
+void launch_classify_runs(hipStream_t st, int mode, uint64_t n, const T *as1, const T *xs1, const T *as2, const T *xs2,
+                          const uint64_t *unit_bits, T m, const RunsOut &ro)
 {
     const uint64_t per_block = (uint64_t)XM_CLASSIFY_BLOCK * 4;
     const uint32_t grid = (uint32_t)((n + per_block - 1) / per_block);
@@ -1911,19 +1900,10 @@ static void launch_classify_runs_t(hipStream_t st, int mode, uint64_t n,
 #undef XM_LAUNCH_RUNS
 }
 
-void launch_classify_runs_i32(hipStream_t st, int mode, uint64_t n,
-                              const int32_t *as1, const int32_t *xs1, const int32_t *as2, const int32_t *xs2,
-                              const uint64_t *unit_bits, int32_t m, const RunsOut &ro)
-{
-    launch_classify_runs_t<int32_t>(st, mode, n, as1, xs1, as2, xs2, unit_bits, m, ro);
-}
-
-void launch_classify_runs_f64(hipStream_t st, int mode, uint64_t n,
-                              const double *as1, const double *xs1, const double *as2, const double *xs2,
-                              const uint64_t *unit_bits, double m, const RunsOut &ro)
-{
-    launch_classify_runs_t<double>(st, mode, n, as1, xs1, as2, xs2, unit_bits, m, ro);
-}
+template void launch_classify_runs<int32_t>(hipStream_t, int, uint64_t, const int32_t *, const int32_t *, const int32_t *,
+                                            const int32_t *, const uint64_t *, int32_t, const RunsOut &);
+template void launch_classify_runs<double>(hipStream_t, int, uint64_t, const double *, const double *, const double *,
+                                           const double *, const uint64_t *, double, const RunsOut &);
 
 void launch_runs_finish(hipStream_t st, int mode, uint64_t *counts_rep, uint64_t *counts, uint64_t *n_out)
 {
