@@ -773,14 +773,109 @@ __device__ __forceinline__ void scatter_granule(const uint32_t w[NSUB], const ui
     }
 }
 
+// The flagship instantiation's form for a granule of strictly interleaved mates (scatter_kernel, FLAGSHIP): the granule is
+// taken 512 records at a time, 32 bits = 8 records = 4 units (nibbles 1, 3, 5, 7) per lane, and the units are ranked where
+// they sit.  Xenograft input is skewed -- most reads belong to one species, bin 0 holds 85 % of the bench's units -- while
+// the ballot form pays one rank chain per occurring bin and 256 records whether the bin has a hundred units there or one.
+// Here the granule has a wave-uniform dominant bin D (its first unit's bin, or the first other one when that holds less
+// than half of the lanes' first units; any choice is correct, 7 included), whose units are ranked by four ballots, one
+// mbcnt chain on the running place (a scalar register) and the in-lane carry.  All other slots need no chain of their own:
+// slot s of the tile has s - (units of D in front of it) other slots in front of it.  At that rank the lane writes
+// (s << 3 | bin) into a wave-private LDS table of 256 words; the table is read back 64 entries a round, one per lane --
+// lane order is record order -- so that each occurring bin costs one ballot and two mbcnt over compacted lanes.  A 7 at an
+// odd record travels through the table like a unit and stores nothing.
+#define XM_SKEW_TILES (XM_GRAN / 512)
+template <bool WIDE>
+__device__ __forceinline__ void scatter_granule_skew(const uint32_t w[XM_SKEW_TILES], uint32_t rec_g, uint32_t lane_base,
+                                                     uint32_t *__restrict__ idx_out, uint32_t n_units, uint32_t *tab, uint16_t *slab)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t D;
+    {
+        const uint32_t first = (w[0] >> 4) & 7u;
+        D = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
+        if (__builtin_popcountll(__ballot(first == D)) < 32) {
+            const uint64_t other = __ballot(first != D);                   // not empty: fewer than 32 lanes hold D
+            D = (uint32_t)__builtin_amdgcn_readlane((int)first, (int)__builtin_ctzll(other));
+        }
+    }
+    uint32_t base[7];
+#pragma unroll
+    for (int b = 0; b < 7; ++b) base[b] = lane_value(lane_base, b);       // base[D] stays as it is: D never reaches the table
+    uint32_t sd = (uint32_t)__builtin_amdgcn_readlane((int)lane_base, (int)D);
+    // The granule's units of D go to one run of idx_out, [sd0, sd0 + their number): they are first written into the wave's
+    // slab at their rank (16-bit record numbers counted from the granule's first, the run shifted by sd0 mod 4 so that
+    // 16-byte-aligned places of idx_out are 8-byte-aligned places of the slab) and copied out with 16-byte stores
+    // (scatter_copy_out): dense dword stores are what bounds this kernel, and four units a lane make them sparse.
+    const uint32_t sd0 = sd, shift = sd0 & 3u;
+    const uint32_t rec1 = lane * 8u + 1u;                                 // the lane's slot j of tile t stands for record rec_g + rec1 + 512 t + 2 j
+#pragma unroll
+    for (int t = 0; t < XM_SKEW_TILES; ++t) {
+        uint32_t bin[4], x[4], nd = 0;
+        bool d[4];
+        uint64_t md[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            bin[j] = (w[t] >> (8 * j + 4)) & 7u;
+            d[j] = bin[j] == D;
+            md[j] = __ballot(d[j]);
+        }
+        uint32_t p = sd;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p = mbcnt64(md[j], p);                 // + units of D in lower lanes
+        const uint32_t slot0 = lane * 4u + sd;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            x[j] = slot0 + (uint32_t)j - p;                                // slots in front that do not hold D: below 256
+            if (d[j]) slab[p - sd0 + shift] = (uint16_t)(rec1 + (uint32_t)(512 * t + 2 * j));      // below XM_GRAN / 2 + 3
+            p += d[j] ? 1u : 0u;                                           // units of D earlier in this lane
+            nd += (uint32_t)__builtin_popcountll(md[j]);
+        }
+        sd += nd;
+        const uint32_t nr = 256u - nd;
+        if (nr == 0u) continue;                                            // wave-uniform: every slot of the tile holds D
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (!d[j]) tab[x[j]] = ((lane * 4u + (uint32_t)j) << 3) | bin[j];
+        lds_settle();
+        auto round = [&](uint32_t k) {                                     // 64 of the nr other slots, one per lane
+            const uint32_t e = tab[k + lane];                              // lanes past the last slot read what is left there
+            const uint32_t eb = lane < nr - k ? (e & 7u) : 7u;
+            uint32_t pos = 0;
+#pragma unroll
+            for (int b = 0; b < 7; ++b) {
+                const uint64_t mb = __ballot(eb == (uint32_t)b);
+                if (mb == 0ull) continue;                                  // wave-uniform
+                pos = (eb == (uint32_t)b) ? mbcnt64(mb, base[b]) : pos;
+                base[b] += (uint32_t)__builtin_popcountll(mb);
+            }
+            if (eb < 7u && (!XM_SCATTER_GUARD || pos < n_units))
+                store_index<WIDE>(idx_out, pos, rec_g + (uint32_t)(512 * t + 1) + ((e >> 3) << 1));
+        };
+        round(0u);
+        if (nr > 64u) {                                                    // wave-uniform, and rare in skewed input
+            round(64u);
+            if (nr > 128u) round(128u);
+            if (nr > 192u) round(192u);
+        }
+        lds_settle();                                                      // the table has been read: the next tile may fill it
+    }
+    lds_settle();                                                          // the slab is complete
+    // never past the number of units, whatever the categories hold; a dominant 7 stores nothing
+    const uint32_t room = sd0 < n_units ? n_units - sd0 : 0u;
+    const uint32_t nd_all = D < 7u ? (sd - sd0 < room || !XM_SCATTER_GUARD ? sd - sd0 : room) : 0u;
+    if (nd_all != 0u) scatter_copy_out<WIDE>(slab, shift, sd0, nd_all, rec_g, idx_out);
+}
+
 // STAGE: this launch may stage (the single-end loop, where every record can be a unit; the paired loops, whose granules
 // hold half as many units at most in ordinary input, use the instantiation without the slab and its bookkeeping, which
 // costs them 2 us per 50 M pairs)
 // LISTS: the six-list output contract -- bin b's units go to lo.p[b] (positions count from the start of that list, so the
 // totals of the bins in front are not needed), bin_offsets receives the list lengths ([7] = all units).
 // Launch shape: one granule per wave (MULTI = false, what every input up to 2^20 granules runs: the body below is the
-// round-4 kernel, whose loads of the granule's counts and of its categories are in flight together and which has no loop
-// state to carry).  MULTI: a wave owns a RUN of `gran_per_wave` consecutive granules (the per-bin places carry over from
+// round-4 kernel, which has no loop state to carry; as compiled it waits for the bin totals and the granule's offsets,
+// runs the scan over them and only then issues the loads of the granule's categories -- two memory round trips.  The
+// FLAGSHIP body issues all of them before its first wait).  MULTI: a wave owns a RUN of `gran_per_wave` consecutive granules (the per-bin places carry over from
 // granule to granule in scalar registers: the scatter leaves base[b] advanced by the granule's units of bin b, so the scan's
 // offsets are read for the wave's first granule only).  Round 5 tried long-lived waves for every input (a dense dword fill
 // gains 4.1 -> 6.0 TB/s from exactly that, tools/probe_streams.hip w) and measured the opposite for this kernel --
@@ -797,15 +892,66 @@ scatter_kernel(const uint8_t *__restrict__ code, uint64_t n, int mode, uint32_t 
     // g_first / last: a launch over the granules [g_first, n_gran) of a chunked call (lists only: their places need the
     // units in front, not the bin totals); the LAST launch of a call publishes the totals and zeroes the part totals
     constexpr bool CAN_STAGE = STAGE && XM_SCATTER_STAGED != 0 && NSUB * 256 == XM_GRAN;
+    // the instantiation of the flagship step (50 M interleaved pairs through xm_classify_compact_dev with bins4) has a body of its own
+    constexpr bool FLAGSHIP = NIB && !STAGE && !LISTS && !MULTI && NSUB * 256 == XM_GRAN;
     __shared__ uint8_t lut_all[NIB ? 1 : XM_BLOCK / 64][64];
     __shared__ uint64_t lptr_all[LISTS ? XM_BLOCK / 64 : 1][8];
     __shared__ __attribute__((aligned(16))) uint16_t slab_all[CAN_STAGE ? XM_BLOCK / 64 : 1][CAN_STAGE ? XM_SLAB_U16 : 4];
     const uint32_t lane = threadIdx.x & 63u;
-    if (last) {   // K2b has consumed the part totals: leave them zeroed for the next count (n_parts cells in each of the 8 x replicas rows)
+    auto zero_parts = [&]() {   // K2b has consumed the part totals: leave them zeroed for the next count (n_parts cells in each of the 8 x replicas rows)
         const uint32_t n_parts = (n_gran + XM_PART_GRAN - 1u) / XM_PART_GRAN, cells = 8u * XM_PART_REPLICAS * n_parts;
         for (uint32_t i = blockIdx.x * XM_BLOCK + threadIdx.x; i < cells; i += gridDim.x * XM_BLOCK)
             part_tot[(i / n_parts) * XM_PART_STRIDE + i % n_parts] = 0u;
+    };
+    if constexpr (FLAGSHIP) {
+        // One granule per wave, categories from bins4, straight to idx_out.  All of the wave's loads -- the bin totals, the
+        // granule's offsets, the granule's categories (32 bits per lane and 512 records) -- are issued before anything
+        // waits on one of them: one memory round trip per wave.  The zeroing of the part totals (the first workgroups of
+        // the last launch: a division loop and stores) comes behind the scatter, where no wave's loads wait for it.
+        __shared__ uint32_t tab_all[XM_BLOCK / 64][256];
+        __shared__ __attribute__((aligned(16))) uint16_t dslab_all[XM_BLOCK / 64][XM_GRAN / 2 + 8];
+        const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        const uint32_t g = g_first + blockIdx.x * (XM_BLOCK / 64) + wave;
+        if (g < n_gran) {                                                 // wave-uniform; no barrier in this kernel
+            const uint32_t tot_ld = (uint32_t)bin_totals[lane & 7u];
+            const uint32_t off_ld = gran_off[(uint64_t)(lane < 7u ? lane : 0u) * gran_stride + g];
+            const uint32_t rec_g = (uint32_t)((uint64_t)g * XM_GRAN);
+            uint32_t w[XM_SKEW_TILES];
+            {   // whole granule blocks exist (records past the end read as 7)
+                const uint32_t *nib = reinterpret_cast<const uint32_t *>(code) + (uint64_t)g * (XM_GRAN / 8) + lane;
+#pragma unroll
+                for (int t = 0; t < XM_SKEW_TILES; ++t) w[t] = nib[t * 64];
+            }
+            // lane b < 8: where bin b starts in idx_out (exclusive prefix of the bin totals) plus what the granules before hold of it
+            const uint32_t tot = (lane < 8u) ? tot_ld : 0u;
+            const uint32_t bin_start = wave_scan_incl(tot) - tot;
+            const uint32_t lane_base = bin_start + ((lane < 7u) ? off_ld : 0u);
+            const uint32_t n_units = lane_value(bin_start, 7);            // slot 7 counts nothing: the total
+            if (g == g_first && last && lane < 8u) bin_offsets[lane] = bin_start;
+            uint32_t all = w[0];
+#pragma unroll
+            for (int t = 1; t < XM_SKEW_TILES; ++t) all &= w[t];
+            if (__ballot((all & 0x07070707u) != 0x07070707u) == 0ull) {   // strictly interleaved mates in all of the granule
+                scatter_granule_skew<WIDE>(w, rec_g, lane_base, idx_out, n_units, tab_all[wave], dslab_all[wave]);
+            } else {
+                // the forms of scatter_granule, 256 records a round and 16 bits per lane: lane l of half h of a tile holds
+                // what lane 32 h + l / 2 loaded
+                uint32_t w16[NSUB];
+#pragma unroll
+                for (int s = 0; s < NSUB; ++s) {
+                    const uint32_t from = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((lane >> 1) + 32u * (uint32_t)(s & 1)) << 2), (int)w[s / 2]);
+                    w16[s] = (from >> (16u * (lane & 1u))) & 0xFFFFu;
+                }
+                uint32_t base[7];
+#pragma unroll
+                for (int b = 0; b < 7; ++b) base[b] = lane_value(lane_base, b);
+                scatter_granule<NSUB, WIDE, true, false, false>(w16, nullptr, rec_g, base, idx_out, n_units, nullptr, nullptr);
+            }
+        }
+        if (last) zero_parts();
+        return;
     }
+    if (last) zero_parts();
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t g0 = g_first + (blockIdx.x * (XM_BLOCK / 64) + wave) * (MULTI ? gran_per_wave : 1u);
     if (g0 >= n_gran) return;                                             // wave-uniform; no barrier in this kernel
