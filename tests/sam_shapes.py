@@ -7,7 +7,9 @@ striding kernels takes.  A plain helper module (no tests, no fixtures): tests/te
 expected_bins to the oracle, tests/test_strip_shapes_gpu.py and tests/test_strip_boundaries_gpu.py run them through the C ABI.
 
 Seeded NumPy only.  Names are letters and digits; every tag of a generated line is one of AS:i / XS:i / ZS:i / NM:i / YT:Z, so no
-optional field holds "AS", "XS", "ZS" or "NM" by accident (the plugins match a tag as a substring of a field, xenomapper.py:186)."""
+optional field holds "AS", "XS", "ZS" or "NM" by accident (the plugins match a tag as a substring of a field, xenomapper.py:186).
+What that leaves out -- the fields themselves on the word and load-step grid of S4, tag text where it must not count, value and CIGAR
+forms, names on every alignment for S5 / S6, the long-record form of S7 -- is in tests/sam_field_shapes.py."""
 import functools
 import re
 

@@ -4,7 +4,6 @@ outcome, same score columns, unit mask, line tables and flagged values -- on ran
 in the middle of files, and on a large synthetic pair of files; then the fused classify pass on the device-resident
 columns against the same pass on the host stripper's columns."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -294,50 +293,17 @@ def test_whole_file_path_with_either_stripper_writes_the_same_bytes(tmp_path):
     assert len(rep) == 4 and all(v["identical"] and v["units"] == 150000 for v in rep.values())
 
 
-def _unpack_cigar(cnt, ops):
-    """Packed CIGAR columns -> the operations of every record (xenomapper_hip.h: a count byte of 255 means "255 or more", the
-    record's operations are then followed by one trailer word n_ops << 4 | 15)."""
-    out, pos = [], 0
-    for c in cnt.tolist():
-        n = c
-        if c == 255:
-            while not ((int(ops[pos + n]) & 15) == 15 and (int(ops[pos + n]) >> 4) == n):
-                n += 1
-        out.append([int(v) for v in ops[pos:pos + n]])
-        pos += n + (1 if c == 255 else 0)
+def device_cigar(s, slot, n):
+    """The slot's packed CIGAR columns as tests/strip_check.py's direct_check reads them: [(nm, operations of every record)]."""
+    from tests.strip_check import unpack_cigar
+    out = []
+    for f in (0, 1):
+        if not n:
+            out.append((np.zeros(0, np.int32), []))
+            continue
+        nm, cnt, _tile, ops = s.cigar_columns(slot, f, n)
+        out.append((nm, unpack_cigar(cnt, ops)))
     return out
-
-
-_PLAIN_INT = re.compile(r"^[+-]?[0-9]{1,10}$")
-
-
-def _plain_int32(text):
-    return bool(_PLAIN_INT.match(text)) and int(text) <= 2**31 - 1 and int(text) >= -(2**31 - 1)
-
-
-def _flag_reason(fields, tag, score_mode):
-    """Why the stripper may (and must) decline to vouch for column `tag` of this line, from the text alone -- None: it must
-    deliver the value.  The plugins' rules (xenomapper.py:176-191, :193-206, :228-256): optional fields fields[11:] that CONTAIN
-    the tag; two of them raise; the value is what follows the last ':'.  The kernels vouch for plain int32 literals only."""
-    opt = fields[11:]
-    if score_mode == 2 and tag == "AS":                               # get_cigarbased_AS_tag: NM (first match) + fields[5]
-        nm = [x for x in opt if "NM" in x]
-        if not nm:
-            return None
-        if len(fields) < 6:
-            return "short"
-        if not _plain_int32(nm[0].split(":")[-1]):
-            return "nonint"
-        if any(int(n) >= 2**28 for n, _op in re.findall(r"([0-9]+)([MIDNSHPX=])", fields[5])):
-            return "biglen"
-        return None
-    name = "ZS" if (score_mode == 1 and tag == "XS") else tag
-    hits = [x for x in opt if name in x]
-    if not hits:
-        return None
-    if len(hits) > 1:
-        return "dup"
-    return None if _plain_int32(hits[0].split(":")[-1]) else "nonint"
 
 
 @settings(max_examples=int(os.environ.get("XM_FUZZ_EXAMPLES", "300")), deadline=None, suppress_health_check=list(HealthCheck))
@@ -345,59 +311,12 @@ def _flag_reason(fields, tag, score_mode):
 def test_gpu_stripper_agrees_with_the_oracle_directly(rig, texts, score_mode, paired, skip):
     """Not through the host stripper: the oracle's restatement of getReadPairs and of the three plugins on the same text --
     record count, walk outcome, unit mask, every score the kernels vouch for (a flag wherever they do not), line spans."""
-    import io
-    from tests.helpers import ORACLE, NEG
+    from tests.strip_check import direct_check
     _ctx, s, _p = rig
     t1, t2 = texts
     b1, b2 = t1.encode("ascii"), t2.encode("ascii")
     got = strip(s, 0, b1, b2, True, True, score_mode, paired, False, 1 << 12, skip)
-    pairs, err = [], None
-    try:
-        for pr in ORACLE.read_pairs(io.StringIO(t1, newline=None), io.StringIO(t2, newline=None), skip):
-            pairs.append(pr)
-    except AssertionError:
-        err = "mismatch"
-    assert got.n == len(pairs) and (got.mismatch_at >= 0) == (err == "mismatch")
-    if err != "mismatch":
-        assert got.ended
-    names = [p[0][0] for p in pairs]
-    cols = got.cols
-    flags = np.unpackbits(np.ascontiguousarray(cols[4] if len(cols) > 4 else got.unit_bits).view(np.uint8), bitorder="little")[:got.n].tolist()
-    assert flags == ([1] * len(pairs) if not paired else [int(i > 0 and names[i] == names[i - 1]) for i in range(len(names))])
-    scorer = [ORACLE.tag_score, ORACLE.tag_score_zs, ORACLE.cigar_score][score_mode]
-    exc = {(k, c) for k, c, _ in got.exc}
-    cig = [None, None]
-    if score_mode == 2 and got.n:
-        for f in (0, 1):
-            nm, cnt, _tile, ops = s.cigar_columns(0, f, got.n)
-            cig[f] = (nm, _unpack_cigar(cnt, ops))
-    raws = (b1, b2)
-    for k, (f1, f2) in enumerate(pairs):
-        for f, fields in enumerate((f1, f2)):
-            st0 = int(got.line_off[f][k])
-            assert raws[f][st0:st0 + int(got.line_len[f][k])].decode().split() == fields
-            assert int(got.norm_len[f][k]) == len("\t".join(fields))
-            for c, tag in ((2 * f, "AS"), (2 * f + 1, "XS")):
-                try:
-                    want, failed = scorer(fields, tag=tag), False
-                except Exception:
-                    want, failed = None, True
-                # a flag must be JUSTIFIED by the text, and a justified flag must be there (an over-flagging stripper -- which the
-                # host path would quietly absorb by re-reading the line -- fails here)
-                why = _flag_reason(fields, tag, score_mode)
-                assert ((k, c) in exc) == (why is not None), (fields, tag, why)
-                if (k, c) in exc:
-                    if why in ("dup", "short"):
-                        assert failed, (fields, tag, why)               # the reference raises (ValueError :189-190 / IndexError)
-                    continue
-                assert not failed, (fields, tag)
-                if score_mode == 2 and tag == "AS":
-                    nm, ops = cig[f][0][k], cig[f][1][k]
-                    have = NEG if nm == -2**31 else -6 * int(nm) - sum(
-                        (5 + 3 * (v >> 4)) if (v & 15) in (1, 2) else (2 * (v >> 4) if (v & 15) == 4 else 0) for v in ops)
-                else:
-                    have = NEG if cols[c][k] == -2**31 else int(cols[c][k])
-                assert have == want, (fields, tag, have, want)
+    direct_check(got, b1, b2, score_mode, paired, skip, device_cigar(s, 0, got.n) if score_mode == 2 else None)
 
 
 def test_closing_a_stripper_leaves_no_dangling_stream_in_the_context():
