@@ -206,6 +206,47 @@ int xmh_parse_pre(xmh_parser *p, const char *buf1, uint64_t len1, int eof1, cons
                   uint64_t n_ops2,
                   int score_mode, int paired, int skip_repeated, int keep_halo, uint64_t max_records, xmh_block *out);
 
+/* ---- SAM lines as BAM alignment records (additive to ABI 5) ---------------------------------------------------------
+ * The rule of csrc/xm_samrec.h, which the device applies behind xm_strip_fetch_bins_bam (include/xenomapper_strip.h): a line
+ * whose fields are separated by single tabs, without its terminator, becomes the record htslib's SAM parser writes for it
+ * (SAM specification 4.2: block_size, the core fields with bin = reg2bin, read_name, CIGAR words, packed SEQ, QUAL, the
+ * optional fields with an `i` value in the smallest type by sign).  This is the checker of the device encoder and the route
+ * for the windows it declines: besides what the device encodes it takes the four host-only forms -- f and B:f values
+ * (strtof), a CIGAR of more than 65535 operations (specification 4.2.2: "<l_seq>S<L>N" and a CG:B:I field behind the other
+ * fields), SEQ bytes outside "=ACMGRSVTWYHKDBN" (a lower-case letter of the table takes the upper-case code, anything else
+ * 15), numbers with a '+', a leading zero or "-0" (their value).  Anything else outside the grammar is an error, reported
+ * and never guessed.
+ *
+ * Lines i = 0 .. n - 1 are text[line_off[i] .. + line_len[i]); names / at / n_refs as xm_bamdev_set_refs takes them (the names
+ * back to back, at[n_refs + 1] positions; a name twice: XMH_ERR_INVALID_ARG).  ref_shift is added to refID and next_refID
+ * where they are >= 0.  device_forms != 0: the host-only forms are declined as the device declines them (XMH_ENC_HOST_*).
+ * The records go to out back to back, sizes[i] (may be NULL) = bytes of record i with its block_size word, *out_len = all of
+ * them; out == NULL: sizes and *out_len only.  XMH_ERR_INVALID_ARG when out_cap is too small.  The first line that is not
+ * encoded ends the call: *bad_line = its index, *reason = XMH_ENC_*, and out / sizes / *out_len hold the lines in front of
+ * it only; otherwise *bad_line = UINT64_MAX. */
+#define XMH_ENC_FIELDS          1   /* fewer than 11 fields */
+#define XMH_ENC_QNAME           2   /* not 1 - 254 bytes */
+#define XMH_ENC_FLAG            3   /* not 0 - 65535 */
+#define XMH_ENC_RNAME           4   /* not '*' and not in the reference list */
+#define XMH_ENC_POS             5   /* not 0 - 2^31 - 1 */
+#define XMH_ENC_MAPQ            6   /* not 0 - 255 */
+#define XMH_ENC_CIGAR           7   /* not '*' and not (digits op)+ with lengths below 2^28 */
+#define XMH_ENC_RNEXT           8
+#define XMH_ENC_PNEXT           9
+#define XMH_ENC_TLEN            10  /* not inside int32 */
+#define XMH_ENC_SEQ             11  /* empty */
+#define XMH_ENC_QUAL            12  /* not '*' and not l_seq bytes in '!' - '~' */
+#define XMH_ENC_AUX             13  /* an optional field that is not TG:T:V of a known type */
+#define XMH_ENC_AUX_RANGE       14  /* a value outside its type's range */
+#define XMH_ENC_SIZE            15  /* the record does not fit block_size */
+#define XMH_ENC_HOST_FLOAT      32  /* device_forms only: an f or B:f field */
+#define XMH_ENC_HOST_LONG_CIGAR 33  /*   more than 65535 CIGAR operations */
+#define XMH_ENC_HOST_SEQ_CODE   34  /*   a SEQ byte outside the 16 upper-case codes */
+#define XMH_ENC_HOST_NUMBER     35  /*   a number that is not canonical */
+int xmh_sam_encode(const uint8_t *text, const uint64_t *line_off, const uint32_t *line_len, uint64_t n, const uint8_t *names,
+                   const uint32_t *at, uint32_t n_refs, int32_t ref_shift, int device_forms, uint8_t *out, uint64_t out_cap,
+                   uint32_t *sizes, uint64_t *out_len, uint64_t *bad_line, int32_t *reason);
+
 #ifdef __cplusplus
 }
 #endif

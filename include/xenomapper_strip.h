@@ -18,6 +18,9 @@
  *
  * Scope: SAM text, all three built-in plugins, the walk with and without --skip_repeated_reads (xenomapper.py:110-117).
  * Windows are shorter than 4 GiB - 64 KiB.  BAM input, windows beyond that and non-ASCII text stay with xenomapper_host.h.
+ * The six outputs come back as text (xm_strip_fetch_bins) or as BAM (xm_strip_fetch_bins_bam: every wanted line encoded as a BAM
+ * alignment record on the device, in BGZF members of stored blocks).  The BAM header made from the @SQ lines, compressed members and
+ * the file path behind classify_sam_files are not part of this interface yet: the caller supplies the reference names.
  *
  * A stripper has two slots so that one window pair can be copied, uploaded and stripped (one host thread) while
  * the block before it is classified and written (another thread); calls on one slot must not overlap.
@@ -32,7 +35,8 @@ extern "C" {
 #endif
 
 #define XMS_ABI_VERSION 4   /* 2: xm_strip_fetch_bins / xm_strip_out_wait.  3: two calls for reading a window ahead (begun behind
-                               a gap, its lead set later).  4: those two withdrawn -- reading ahead measured no better */
+                               a gap, its lead set later).  4: those two withdrawn -- reading ahead measured no better.  Additive since,
+                               the version unchanged: xm_strip_set_refs / xm_strip_fetch_bins_bam */
 #define XMS_SLOTS 2
 #define XMS_MAX_WINDOW 0xFFFF0000ull
 
@@ -129,6 +133,55 @@ typedef struct {
 } xm_strip_bins;
 int xm_strip_fetch_bins(xm_strip *s, int slot, uint64_t n_records, int paired, uint32_t sink_mask, xm_strip_bins *out);
 int xm_strip_out_wait(xm_strip *s, int slot);      /* blocks until the stream asked for last has arrived (any thread) */
+
+/*
+ * The six outputs as BAM.  xm_strip_set_refs: the reference names of file 0 / 1, as xm_bamdev_set_refs takes them (the names back
+ * to back, at[n_refs + 1] positions), once per file and for both slots; an open-addressed table of them is built on the host and
+ * uploaded (XM_ERR_INVALID_ARG: a name twice).  Not to be called while a slot is in use.
+ * xm_strip_fetch_bins_bam, after xm_strip_classify, is xm_strip_fetch_bins with every wanted line encoded as the BAM alignment record
+ * htslib's SAM parser writes for it (the rule: csrc/xm_samrec.h; xmh_sam_encode of xenomapper_host.h is the same rule on the host)
+ * and the records framed as xm_bamdev_fetch_bins_bam frames them: bin b's bytes = text[bin_off[b] .. bin_off[b + 1]), a whole number
+ * of complete BGZF members of one stored block each, none when the bin has no wanted unit; every member but a bin's last holds
+ * block_payload record bytes (64 .. 65280; 0 = 65280), so a record may span members.  ref_shift is added to refID and next_refID of
+ * file 2's records in bin 4 where they are >= 0.  The caller puts a BAM header in front and the end-of-file member behind.
+ * status 0: on its way (xm_strip_out_wait).  Otherwise nothing was copied, and the window is the host's (xmh_sam_encode):
+ *   1: a wanted line the device does not encode -- reason = XMS_ENC_*, declined_record / declined_file (0, 1) = the first such line
+ *      in the order of the output; a host-only form (XMS_ENC_HOST_*: an f or B:f field, more than 65535 CIGAR operations, a SEQ byte
+ *      outside the 16 upper-case codes, a number that is not canonical) or a line outside the grammar, which the host reports
+ *   2: more bytes than the slot's buffers hold
+ *   3: a wanted line that is not XMS_LINE_NORMAL (looked at before 1)
+ * Only wanted lines decide.  XM_ERR_INVALID_ARG without the references of a file whose lines are wanted.  The call shares the slot's
+ * output stream with xm_strip_fetch_bins: either may follow the other on one classified block.
+ */
+#define XMS_ENC_FIELDS          1   /* fewer than 11 fields */
+#define XMS_ENC_QNAME           2   /* not 1 - 254 bytes */
+#define XMS_ENC_FLAG            3
+#define XMS_ENC_RNAME           4   /* not '*' and not in the reference list */
+#define XMS_ENC_POS             5
+#define XMS_ENC_MAPQ            6
+#define XMS_ENC_CIGAR           7
+#define XMS_ENC_RNEXT           8
+#define XMS_ENC_PNEXT           9
+#define XMS_ENC_TLEN            10
+#define XMS_ENC_SEQ             11
+#define XMS_ENC_QUAL            12  /* not '*' and not l_seq bytes in '!' - '~' */
+#define XMS_ENC_AUX             13  /* an optional field that is not TG:T:V of a known type */
+#define XMS_ENC_AUX_RANGE       14  /* a value outside its type's range */
+#define XMS_ENC_SIZE            15
+#define XMS_ENC_HOST_FLOAT      32
+#define XMS_ENC_HOST_LONG_CIGAR 33
+#define XMS_ENC_HOST_SEQ_CODE   34
+#define XMS_ENC_HOST_NUMBER     35
+int xm_strip_set_refs(xm_strip *s, int file, const uint8_t *names, const uint32_t *at, uint32_t n_refs);
+typedef struct {
+    const uint8_t *text;
+    uint64_t bin_off[8];
+    int32_t  status, reason;
+    uint64_t declined_record;
+    int32_t  declined_file, reserved;
+} xm_strip_bam_bins;
+int xm_strip_fetch_bins_bam(xm_strip *s, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload,
+                            int32_t ref_shift, xm_strip_bam_bins *out);
 
 /* Bring the first n_records of the slot's score columns and ceil(n/64) words of the unit mask to the host (for records
  * the caller must patch by the text rules).  Any pointer may be NULL. */

@@ -147,6 +147,8 @@ def lib():
         "xm_strip_cigar_columns": ([P, I, I, U64, P, P, P, P, U64, ctypes.POINTER(U64)], I),
         "xm_strip_classify": ([P, I, I, U64, I32, ctypes.POINTER(P), ctypes.POINTER(P), P, P], I),
         "xm_strip_fetch_bins": ([P, I, U64, I, ctypes.c_uint32, P], I),
+        "xm_strip_set_refs": ([P, I, P, P, ctypes.c_uint32], I),
+        "xm_strip_fetch_bins_bam": ([P, I, U64, I, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, P], I),
         "xm_strip_out_wait": ([P, I], I),
         "xm_strip_columns": ([P, I, U64, P, P, P, P, P], I),
         "xm_strip_device_columns": ([P, I, P], I),
@@ -200,7 +202,7 @@ EXPORTED = ("xm_abi_version", "xm_strerror", "xm_last_hip_error", "xm_ctx_create
             "xm_comm_unique_id", "xm_comm_init", "xm_comm_destroy", "xm_comm_size", "xm_allreduce_counts",
             "xm_timing_enable", "xm_timing_select", "xm_timing_reset", "xm_timing_read",
             "xms_abi_version", "xm_strip_create", "xm_strip_destroy", "xm_strip_reserve", "xm_strip_staging", "xm_strip_upload", "xm_strip_run",
-            "xm_strip_classify", "xm_strip_fetch_bins", "xm_strip_out_wait", "xm_strip_columns", "xm_strip_cigar_columns", "xm_strip_device_columns", "xm_strip_last_error",
+            "xm_strip_classify", "xm_strip_fetch_bins", "xm_strip_set_refs", "xm_strip_fetch_bins_bam", "xm_strip_out_wait", "xm_strip_columns", "xm_strip_cigar_columns", "xm_strip_device_columns", "xm_strip_last_error",
             "xm_bgzf_index", "xm_bgzf_index_prefix", "xm_bgzf_inflate_dev", "xm_bgzf_inflate_walk_dev", "xm_bgzf_crc32_dev", "xm_bgzf_strerror",
             "xm_bgzf_deflate_work_bytes", "xm_bgzf_deflate_dev", "xm_bgzf_compress",
             "xm_bamdev_create", "xm_bamdev_destroy", "xm_bamdev_reserve", "xm_bamdev_staging", "xm_bamdev_run", "xm_bamdev_raw_wait", "xm_bamdev_fetch_raw", "xm_bamdev_raw", "xm_bamdev_fetch_wanted", "xm_bamdev_fetch_text", "xm_bamdev_fetch_bins", "xm_bamdev_fetch_bins_bam", "xm_bamdev_fetch_bins_bamz", "xm_bamdev_set_refs", "xm_bamdev_upload", "xm_bamdev_classify",
@@ -847,6 +849,11 @@ class _BamDevBins(ctypes.Structure):          # xm_bamdev_bins and xm_strip_bins
     _fields_ = [("text", ctypes.c_void_p), ("bin_off", ctypes.c_uint64 * 8), ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class _StripBamBins(ctypes.Structure):        # xm_strip_bam_bins
+    _fields_ = [("text", ctypes.c_void_p), ("bin_off", ctypes.c_uint64 * 8), ("status", ctypes.c_int32), ("reason", ctypes.c_int32),
+                ("declined_record", ctypes.c_uint64), ("declined_file", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class _StripBlock(ctypes.Structure):
     _fields_ = [("n_records", ctypes.c_uint64), ("consumed1", ctypes.c_uint64), ("consumed2", ctypes.c_uint64),
                 ("consumed_lines1", ctypes.c_uint64), ("consumed_lines2", ctypes.c_uint64),
@@ -1047,6 +1054,27 @@ class Stripper(_FrontEnd):
         next fetch on the slot); status 2 / 3: this window is the host writer's (more text than the buffers hold / a wanted line
         that needs its white space re-joined)."""
         return self._fetch_bins("fetch_bins", int(slot), int(n_records), int(bool(paired)), int(sink_mask))     # (xm_strip_bins: the same layout)
+
+    def set_refs(self, file, names):
+        """The reference names of file 0 / 1 (a list of bytes, in reference-id order; no name twice): what fetch_bins_bam looks RNAME
+        and RNEXT up in."""
+        blob = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)
+        at = np.zeros(len(names) + 1, dtype=np.uint32)
+        if names:
+            at[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64).astype(np.uint32)
+        self._check(self._L.xm_strip_set_refs(self._h, int(file), _np_ptr(blob), _np_ptr(at), len(names)), "xm_strip_set_refs")
+
+    def fetch_bins_bam(self, slot, n_records, paired, sink_mask, block_payload=0, ref_shift=0):
+        """After classify(): the six outputs as BAM, every wanted line encoded as an alignment record on the device
+        (xm_strip_fetch_bins_bam) -> (status, stream, bin_off, declined): bin b's bytes = stream[bin_off[b]:bin_off[b + 1]], whole
+        BGZF members of stored blocks (valid after out_wait()).  status 1: declined = (record, file, XMS_ENC_* reason) of the
+        first wanted line the device does not encode; 2: more bytes than the buffers hold; 3: a wanted line that is not
+        '\\t'.join(fields) -- then this window is the host encoder's (_host.sam_encode)."""
+        t = _StripBamBins()
+        self._check(self._L.xm_strip_fetch_bins_bam(self._h, int(slot), int(n_records), int(bool(paired)), int(sink_mask), int(block_payload),
+                                                    int(ref_shift), ctypes.byref(t)), "xm_strip_fetch_bins_bam")
+        declined = (int(t.declined_record), int(t.declined_file), int(t.reason)) if t.status == 1 else None
+        return self._bins_result(t) + (declined,)
 
     def out_wait(self, slot):
         self._check(self._L.xm_strip_out_wait(self._h, int(slot)), "xm_strip_out_wait")

@@ -16,7 +16,7 @@ ERR_NON_ASCII = -3
 
 EXPORTED = ("xmh_abi_version", "xmh_strerror", "xmh_default_threads", "xmh_parser_create", "xmh_parser_destroy", "xmh_parse", "xmh_emit",
             "xmh_bam_open", "xmh_bam_open_header", "xmh_bam_close", "xmh_bam_header", "xmh_bam_read", "xmh_bam_read_pre", "xmh_parse_pre",
-            "xmh_copy", "xmh_pread", "xmh_adopt_lines", "xmh_bam_records_start", "xmh_bam_print", "xmh_bam_walk")
+            "xmh_copy", "xmh_pread", "xmh_adopt_lines", "xmh_bam_records_start", "xmh_bam_print", "xmh_bam_walk", "xmh_sam_encode")
 NEED_TEXT = 1
 # xmh_pre (include/xenomapper_host.h): what the BAM decoder knows about every line it prints
 PRE_DTYPE = np.dtype([("line_len", np.uint32), ("name_len", np.uint16), ("flags", np.uint8), ("ex_as", np.uint8),
@@ -90,6 +90,8 @@ def lib():
         L.xmh_copy.argtypes = [_P, _P, _P, ctypes.c_uint64]
         L.xmh_pread.argtypes = [_P, ctypes.c_int, ctypes.c_uint64, _P, ctypes.c_uint64]
         L.xmh_adopt_lines.argtypes = [_P, ctypes.c_uint64] + [_P] * 8
+        L.xmh_sam_encode.argtypes = [_P, _P, _P, ctypes.c_uint64, _P, _P, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int, _P, ctypes.c_uint64,
+                                     _P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int32)]
         _lib = L
     return _lib
 
@@ -254,6 +256,41 @@ class Parser(object):
         if rc != 0:
             raise RuntimeError("xmh_emit: " + self._L.xmh_strerror(rc).decode())
         return out
+
+
+def ref_blob(names):
+    """A list of reference names (str or bytes) as xm_*_set_refs and xmh_sam_encode take it -> (uint8 blob, uint32 at[n + 1])."""
+    raw = [n.encode("latin-1") if isinstance(n, str) else bytes(n) for n in names]
+    at = np.zeros(len(raw) + 1, dtype=np.uint32)
+    at[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+    blob = np.frombuffer(b"".join(raw) + b"\0" * 16, dtype=np.uint8).copy()
+    return blob, at
+
+
+def sam_encode(text, line_off, line_len, names, ref_shift=0, device_forms=False):
+    """xmh_sam_encode: the lines text[line_off[i] : line_off[i] + line_len[i]] (text: uint8 array or bytes) as BAM alignment records
+    -> (records back to back as bytes, sizes uint32[k], bad_line or None, reason).  With a bad line, k = bad_line: the records in
+    front of it.  device_forms: decline what the device encoder declines (the host-only forms)."""
+    text = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+    off = np.ascontiguousarray(line_off, dtype=np.uint64)
+    ln = np.ascontiguousarray(line_len, dtype=np.uint32)
+    n = off.shape[0]
+    blob, at = ref_blob(names)
+    sizes = np.zeros(max(n, 1), dtype=np.uint32)
+    total, bad, reason = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int32()
+    L = lib()
+
+    def call(out, cap):
+        rc = L.xmh_sam_encode(text.ctypes.data_as(_P), off.ctypes.data_as(_P), ln.ctypes.data_as(_P), n, blob.ctypes.data_as(_P),
+                              at.ctypes.data_as(_P), len(names), int(ref_shift), int(bool(device_forms)), out, cap,
+                              sizes.ctypes.data_as(_P), ctypes.byref(total), ctypes.byref(bad), ctypes.byref(reason))
+        if rc != 0:
+            raise ValueError("xmh_sam_encode: " + L.xmh_strerror(rc).decode())
+    call(None, 0)
+    out = np.zeros(max(int(total.value), 1), dtype=np.uint8)
+    call(out.ctypes.data_as(_P), int(total.value))
+    k = n if bad.value == 0xFFFFFFFFFFFFFFFF else int(bad.value)
+    return out[:int(total.value)].tobytes(), sizes[:k].copy(), (None if k == n and bad.value == 0xFFFFFFFFFFFFFFFF else k), int(reason.value)
 
 
 def bam_walk(raw_address, length, start, rec_off):

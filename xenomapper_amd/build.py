@@ -16,7 +16,7 @@ HIP_LIB = os.path.join(PKG, "libxenomapper_hip.so")
 HOST_LIB = os.path.join(PKG, "libxenomapper_host.so")
 
 HIP_SOURCES = ["xm_kernels.hip", "xm_api.hip", "xm_strip.hip", "xm_inflate.hip", "xm_deflate.hip", "xm_bamdev.hip"]
-HOST_SOURCES = ["xm_sam.cpp", "xm_bam.cpp"]
+HOST_SOURCES = ["xm_sam.cpp", "xm_bam.cpp", "xm_samenc.cpp"]
 
 
 def _hipcc():
@@ -37,6 +37,7 @@ def build_hip(force=False, verbose=False):
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
     deps = srcs + [os.path.join(CSRC, "xm_kernels.h"), os.path.join(CSRC, "xm_inflate_core.h"), os.path.join(CSRC, "xm_deflate_core.h"), os.path.join(CSRC, "xm_bgzf_pack.h"),
                    os.path.join(CSRC, "xm_bamrec.h"), os.path.join(CSRC, "xm_fmtg.h"), os.path.join(CSRC, "xm_pinned.h"), os.path.join(CSRC, "xm_gather.h"), os.path.join(CSRC, "xm_slot.h"),
+                   os.path.join(CSRC, "xm_samrec.h"), os.path.join(CSRC, "xm_bamframe.h"),
                    os.path.join(REPO, "include", "xenomapper_hip.h"), os.path.join(REPO, "include", "xenomapper_strip.h"),
                    os.path.join(REPO, "include", "xenomapper_bgzf.h")]
     if not force and not _stale(HIP_LIB, deps):
@@ -76,7 +77,7 @@ def build_host(force=False, verbose=False):
     srcs = [os.path.join(CSRC, s) for s in HOST_SOURCES]
     if not all(os.path.exists(s) for s in srcs):
         return None
-    deps = srcs + [os.path.join(REPO, "include", "xenomapper_host.h"), os.path.join(CSRC, "xm_pool.h")]
+    deps = srcs + [os.path.join(REPO, "include", "xenomapper_host.h"), os.path.join(CSRC, "xm_pool.h"), os.path.join(CSRC, "xm_samrec.h")]
     if not force and not _stale(HOST_LIB, deps):
         return HOST_LIB
     cmd = ["g++", "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall", "-Wextra",

@@ -32,6 +32,7 @@
 #include <new>
 
 #include "../../include/xenomapper_bgzf.h"
+#include "xm_bamframe.h"              // the stored-member frames (O1, O3)
 #include "xm_bamrec.h"
 #include "xm_bgzf_pack.h"                // bgzf_pack_kernel (Z5)
 #include "xm_fmtg.h"
@@ -590,44 +591,8 @@ line_fill_kernel(const uint8_t *__restrict__ raw1, const uint8_t *__restrict__ r
 // block header (01 LEN NLEN), 8 of CRC-32 and ISIZE -- so payload byte r of bin b lies at F_b + (r / P) * (P + 31) + 23 + r % P.
 // O1 derives F_b and the members' descriptors, O2 copies every record to where it belongs (a wave per record, split at the member
 // seams), the CRC kernel of the inflate path reads the payloads where they lie, O3 writes the frames around them.
-constexpr uint32_t BGZF_HEAD = 18, STORED_HEAD = 5, BGZF_TAIL = 8, BGZF_FRAME = BGZF_HEAD + STORED_HEAD + BGZF_TAIL;
-
-// what O1 leaves for O2: F_b (b = 0..6; [7] = the framed total) and the index of every bin's first member ([7] = how many there are)
-struct BamLayout { uint32_t frame_start[8], member_start[8]; };
-
-__device__ __forceinline__ void bam_layout_of(const uint32_t *__restrict__ starts, uint32_t P, BamLayout &l)
-{
-    uint32_t f = 0, m = 0;
-#pragma unroll
-    for (uint32_t b = 0; b < 7u; ++b) {
-        l.frame_start[b] = f; l.member_start[b] = m;
-        const uint32_t len = starts[b + 1u] - starts[b], members = (len + P - 1u) / P;
-        f += len + members * BGZF_FRAME;
-        m += members;
-    }
-    l.frame_start[7] = f; l.member_start[7] = m;
-}
-
-// O1: a lane per member: its descriptor for the CRC kernel (out_off: the payload's first byte in the framed stream, isize: its bytes)
-__global__ void __launch_bounds__(256)
-bam_layout_kernel(const uint32_t *__restrict__ starts, uint32_t P, uint32_t n_members, BamLayout *__restrict__ layout,
-                  xm_bgzf_block *__restrict__ members)
-{
-    BamLayout l;
-    bam_layout_of(starts, P, l);
-    const uint32_t m = blockIdx.x * 256u + threadIdx.x;
-    if (m == 0u) *layout = l;
-    if (m >= n_members || m >= l.member_start[7]) return;
-    uint32_t b = 0;
-#pragma unroll
-    for (uint32_t k = 1; k < 7u; ++k) b += (l.member_start[k] <= m) ? 1u : 0u;
-    const uint32_t k = m - l.member_start[b], len = starts[b + 1u] - starts[b], left = len - k * P;
-    xm_bgzf_block d;
-    d.cdata_off = 0; d.cdata_len = 0;
-    d.out_off = (uint64_t)l.frame_start[b] + (uint64_t)k * (P + BGZF_FRAME) + BGZF_HEAD + STORED_HEAD;
-    d.isize = left < P ? left : P;
-    members[m] = d;
-}
+// (BGZF_HEAD / STORED_HEAD / BGZF_TAIL / BGZF_FRAME, BamLayout, bam_layout_of, O1 bam_layout_kernel and O3 bam_frame_kernel: xm_bamframe.h,
+// shared with the SAM front end's xm_strip_fetch_bins_bam)
 
 // O2's copy of one record: `size` bytes at src become payload bytes [r, r + size) of the bin whose frames begin at `frames`.  A lane
 // takes 16 bytes of the record per step (an unaligned dwordx4 load; the last one of a record may reach up to 15 bytes behind it,
@@ -711,27 +676,6 @@ record_fill_kernel(const uint8_t *__restrict__ raw1, const uint8_t *__restrict__
     }
 }
 
-// O3: a lane per member: the gzip header with the BC subfield (BSIZE = member size - 1), the stored block's header, CRC-32 and ISIZE
-__global__ void __launch_bounds__(256)
-bam_frame_kernel(const xm_bgzf_block *__restrict__ members, const uint32_t *__restrict__ crc, uint32_t n_members, uint8_t *__restrict__ out,
-                 uint32_t out_cap)
-{
-    const uint32_t m = blockIdx.x * 256u + threadIdx.x;
-    if (m >= n_members) return;
-    const xm_bgzf_block d = members[m];
-    const uint32_t len = d.isize, bsize = len + BGZF_FRAME - 1u;
-    if (d.out_off < BGZF_HEAD + STORED_HEAD || d.out_off + len + BGZF_TAIL > out_cap || len > 0xFFFFu - BGZF_FRAME + 1u) return;
-    uint8_t *h = out + d.out_off - (BGZF_HEAD + STORED_HEAD);
-    const uint8_t head[BGZF_HEAD + STORED_HEAD] = {
-        0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)bsize, (uint8_t)(bsize >> 8),
-        1, (uint8_t)len, (uint8_t)(len >> 8), (uint8_t)~len, (uint8_t)(~len >> 8)};
-#pragma unroll
-    for (uint32_t k = 0; k < BGZF_HEAD + STORED_HEAD; ++k) h[k] = head[k];
-    uint8_t *t = out + d.out_off + len;
-    const uint32_t c = crc[m];
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k) { t[k] = (uint8_t)(c >> (8u * k)); t[4u + k] = (uint8_t)(len >> (8u * k)); }
-}
 
 // ---- Z: the six outputs as compressed BAM (xm_bamdev_fetch_bins_bamz): the same payloads, each member deflated -----------------------
 // O's scan and O's members, but the payloads are gathered WITHOUT frames into a buffer of their own (Z2 = O2 with FRAMED = false:

@@ -23,6 +23,8 @@
 //                     as the packed columns the classify kernel reads (xenomapper_hip.h)
 //   S8 summary_kernel one lane: the walk's outcome (records, consumed bytes, ended / starved / mismatch) as xmh_parse reports it
 // The score columns and the unit mask never leave the device: xm_strip_classify runs the fused classify pass on them.
+// Behind it, G gathers the six outputs as text (xm_strip_fetch_bins) and E encodes them as BAM records (xm_strip_fetch_bins_bam:
+// E1 sizes, E2 writes, F frames; the rule is csrc/xm_samrec.h).
 #include "../../include/xenomapper_strip.h"
 
 #include <hip/hip_runtime.h>
@@ -31,8 +33,20 @@
 #include <climits>
 #include <cstring>
 #include <new>
+#include <vector>
 
+#include "xm_bamframe.h"
+#include "xm_samrec.h"
 #include "xm_slot.h"
+
+static_assert(XMS_ENC_FIELDS == xmsam::ENC_FIELDS && XMS_ENC_QNAME == xmsam::ENC_QNAME && XMS_ENC_FLAG == xmsam::ENC_FLAG &&
+              XMS_ENC_RNAME == xmsam::ENC_RNAME && XMS_ENC_POS == xmsam::ENC_POS && XMS_ENC_MAPQ == xmsam::ENC_MAPQ &&
+              XMS_ENC_CIGAR == xmsam::ENC_CIGAR && XMS_ENC_RNEXT == xmsam::ENC_RNEXT && XMS_ENC_PNEXT == xmsam::ENC_PNEXT &&
+              XMS_ENC_TLEN == xmsam::ENC_TLEN && XMS_ENC_SEQ == xmsam::ENC_SEQ && XMS_ENC_QUAL == xmsam::ENC_QUAL &&
+              XMS_ENC_AUX == xmsam::ENC_AUX && XMS_ENC_AUX_RANGE == xmsam::ENC_AUX_RANGE && XMS_ENC_SIZE == xmsam::ENC_SIZE &&
+              XMS_ENC_HOST_FLOAT == xmsam::ENC_HOST_FLOAT && XMS_ENC_HOST_LONG_CIGAR == xmsam::ENC_HOST_LONG_CIGAR &&
+              XMS_ENC_HOST_SEQ_CODE == xmsam::ENC_HOST_SEQ_CODE && XMS_ENC_HOST_NUMBER == xmsam::ENC_HOST_NUMBER,
+              "the reason codes of xenomapper_strip.h are xm_samrec.h's");
 
 namespace {
 
@@ -839,6 +853,142 @@ sam_line_copy_kernel(const uint8_t *__restrict__ text1, const uint8_t *__restric
     }
 }
 
+// ---- E: the six outputs as BAM (xm_strip_fetch_bins_bam): every wanted line encoded as a BAM alignment record --------------------
+// G's unit lists and G's scan with the records' sizes in place of the line lengths.  E1 sizes every wanted line (step 1 of
+// xm_samrec.h, which reads and checks the whole line), the scan places the units -- it IS the layout of the six payloads back to
+// back, as in Z2 of xm_bamdev_fetch_bins_bamz -- E2 writes the records into a payload buffer without frames (what xm_bgzf_deflate_dev
+// and bgzf_pack_kernel can take next), F copies the payload into members of P bytes between their frames, then the CRC kernel of the
+// inflate path and the frame kernel of xm_bamframe.h run as they do behind the BAM front end.
+// A unit holds up to four wanted lines, in the order of the output: file 1's line(s), then file 2's; a paired unit is records i - 1
+// and i.  Line q of a unit: file q / per_file, record j = q % per_file of the unit (per_file = 2 when paired, else 1).
+struct EncFile {
+    const uint8_t *text;
+    const uint32_t *loff, *llen;
+    const uint8_t *lflag;
+    xmsam::RefHash refs;
+    uint32_t *esize, *eseq, *elseq;                    // per record: xmsam::Sized of its line (E1 -> E2)
+};
+
+struct EncUnit { bool wanted; uint32_t f, j, i, r, files, bin; };
+
+__device__ __forceinline__ EncUnit enc_unit(uint32_t p, uint32_t q, const uint32_t *__restrict__ idx, const unsigned long long *__restrict__ off,
+                                            uint32_t n_units, uint32_t n_records, int paired, uint32_t sink_mask)
+{
+    EncUnit u;
+    u.f = paired ? q >> 1 : q; u.j = paired ? q & 1u : 0u;
+    u.wanted = false; u.i = 0; u.r = 0; u.files = 0; u.bin = 0;
+    if (p >= n_units) return u;
+    u.i = idx[p];
+    u.bin = bin_of_place(p, off);
+    u.files = files_of_bin(u.bin, sink_mask);
+    if (u.i >= n_records || (paired && u.i == 0u)) return u;
+    u.r = paired ? u.i - 1u + u.j : u.i;
+    u.wanted = ((u.files >> u.f) & 1u) != 0u;
+    return u;
+}
+
+// E1: a lane per (unit, line of the unit).  Sizing a line is a serial walk over its bytes (every field is checked, a number's value
+// decides the bytes it takes), so a lane per line, as S4; the two or four lanes of a unit are neighbours in a wave and add their
+// sizes by shuffles.  declined: the least (unit place, file, record of the unit) of the lines the device does not encode, with the
+// reason in its low byte.
+__global__ void __launch_bounds__(256)
+sam_enc_size_kernel(const EncFile f0, const EncFile f1, const uint32_t *__restrict__ idx, const unsigned long long *__restrict__ off,
+                    uint32_t n_units, uint32_t n_records, int paired, uint32_t sink_mask, uint32_t *__restrict__ usize,
+                    unsigned long long *__restrict__ total64, uint32_t *__restrict__ not_normal, unsigned long long *__restrict__ declined)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x, per = paired ? 4u : 2u;
+    const uint32_t p = t / per, q = t % per;
+    const EncUnit u = enc_unit(p, q, idx, off, n_units, n_records, paired, sink_mask);
+    uint32_t s = 0, odd = 0;
+    if (u.wanted) {
+        const EncFile &f = u.f ? f1 : f0;
+        if ((f.lflag[u.r] & XMS_LINE_NORMAL) == 0u) {
+            odd = 1u;
+        } else {
+            const xmsam::Sized sz = xmsam::size_of<false>(f.text + f.loff[u.r], f.llen[u.r], f.refs);
+            if (sz.reason != xmsam::ENC_OK)
+                atomicMin(declined, ((unsigned long long)p << 10) | ((unsigned long long)u.f << 9) | ((unsigned long long)u.j << 8) |
+                                        (unsigned long long)(sz.reason & 0xFF));
+            s = sz.size;
+            f.esize[u.r] = sz.size; f.eseq[u.r] = sz.seq_off; f.elseq[u.r] = sz.l_seq;
+        }
+    }
+    uint32_t unit = s + __shfl_xor(s, 1, 64);
+    if (paired) unit += __shfl_xor(unit, 2, 64);
+    if (q == 0u && p < n_units) usize[p] = unit;
+    unsigned long long tot = s;
+    for (int d = 32; d; d >>= 1) tot += __shfl_xor(tot, d, 64);
+    if ((threadIdx.x & 63u) == 0u && tot) atomicAdd(total64, tot);
+    if (__any(odd != 0u) && (threadIdx.x & 63u) == 0u) atomicOr(not_normal, 1u);
+}
+
+// E2: a wave per (unit, line of the unit), the shape of sam_line_copy_kernel and record_fill_kernel.  SEQ and QUAL are most of a
+// record (300 of the ~370 bytes of a 150-base read) and each of their output bytes depends on one or two input bytes alone: the
+// wave packs them, a lane per output byte, 64 bytes per step, loads and stores of neighbouring lanes next to each other.  What is
+// left -- the core fields, the name, the CIGAR words, the optional fields -- is a serial walk in which a number's value decides how
+// many bytes it takes; lane 0 does it (step 2 of xm_samrec.h, SEQ / QUAL found through what E1 left, not scanned again) while the
+// other lanes wait.  A lane per record would keep all lanes busy there but scatter the SEQ / QUAL traffic, the larger part, over 64
+// cache lines per instruction; the idle lanes cost issue slots of a kernel that is bound by its memory traffic.
+__global__ void __launch_bounds__(256)
+sam_enc_write_kernel(const EncFile f0, const EncFile f1, const uint32_t *__restrict__ idx, const unsigned long long *__restrict__ off,
+                     uint32_t n_units, uint32_t n_records, int paired, uint32_t sink_mask, const uint32_t *__restrict__ usize,
+                     const uint32_t *__restrict__ uplace, int32_t ref_shift, uint8_t *__restrict__ out, uint32_t out_cap)
+{
+    const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u, per = paired ? 4u : 2u;
+    const uint32_t p = w / per, q = w % per;
+    const EncUnit u = enc_unit(p, q, idx, off, n_units, n_records, paired, sink_mask);
+    if (!u.wanted) return;
+    const EncFile &f = u.f ? f1 : f0;
+    const uint32_t size = f.esize[u.r], unit = usize[p];
+    if (size == 0u) return;
+    uint32_t before = 0;                                                        // the unit's records in front of this one
+    if (u.f == 1u && (u.files & 1u)) before += f0.esize[u.i] + (paired ? f0.esize[u.i - 1u] : 0u);
+    if (u.j == 1u) before += f.esize[u.i - 1u];
+    const uint32_t at = uplace[p];
+    if (before > unit || size > unit - before || at > out_cap || unit > out_cap - at) return;    // (the total was checked before the launch)
+    const uint8_t *line = f.text + f.loff[u.r];
+    uint8_t *dst = out + at + before;
+    xmsam::Bulk bulk;
+    bulk.seq_src = bulk.l_seq = bulk.seq_dst = bulk.qual_src = bulk.qual_dst = 0u;
+    int32_t rc = xmsam::ENC_OK;
+    if (lane == 0u) {
+        const xmsam::Sized sz{size, xmsam::ENC_OK, f.eseq[u.r], f.elseq[u.r]};
+        rc = xmsam::write<false>(line, f.llen[u.r], f.refs, (u.f == 1u && u.bin == 4u) ? ref_shift : 0, sz, dst, &bulk);
+    }
+    rc = __shfl(rc, 0, 64);
+    if (rc != xmsam::ENC_OK) return;
+    const uint32_t seq_src = __shfl(bulk.seq_src, 0, 64), l_seq = __shfl(bulk.l_seq, 0, 64), seq_dst = __shfl(bulk.seq_dst, 0, 64),
+                   qual_src = __shfl(bulk.qual_src, 0, 64), qual_dst = __shfl(bulk.qual_dst, 0, 64);
+    if ((uint64_t)qual_dst + l_seq > size) return;                              // (write() checked it against the same size)
+    xmsam::pack_seq(line + seq_src, l_seq, dst + seq_dst, lane, 64u);
+    xmsam::pack_qual(qual_src == ~0u ? nullptr : line + qual_src, l_seq, dst + qual_dst, lane, 64u);
+}
+
+// F: a workgroup per member: its payload bytes from the unframed buffer to between its frames, 16 bytes per lane and step (one
+// unaligned dwordx4 load and store: neither side is aligned, a member's payload begins 23 bytes behind its frame), the last bytes of
+// a member one by one.  A record may span members: the seam is wherever byte k * P of the bin falls.
+typedef uint32_t v4u32_un __attribute__((ext_vector_type(4), aligned(1)));
+__global__ void __launch_bounds__(256)
+sam_enc_frame_copy_kernel(const uint8_t *__restrict__ pay, uint32_t pay_bytes, const uint32_t *__restrict__ starts, const BamLayout *__restrict__ layout,
+                          const xm_bgzf_block *__restrict__ members, uint32_t n_members, uint32_t P, uint8_t *__restrict__ out, uint32_t out_cap)
+{
+    const uint32_t m = blockIdx.x;
+    if (m >= n_members || m >= layout->member_start[7]) return;
+    uint32_t b = 0;
+#pragma unroll
+    for (uint32_t k = 1; k < 7u; ++k) b += (layout->member_start[k] <= m) ? 1u : 0u;
+    const xm_bgzf_block d = members[m];
+    const uint64_t src_at = (uint64_t)starts[b] + (uint64_t)(m - layout->member_start[b]) * P;
+    const uint32_t len = d.isize;
+    if (len > P || src_at + len > pay_bytes || d.out_off < BGZF_HEAD + STORED_HEAD || d.out_off + len + BGZF_TAIL > out_cap) return;
+    const uint8_t *src = pay + src_at;
+    uint8_t *dst = out + d.out_off;
+    for (uint32_t k = threadIdx.x * 16u; k < len; k += 256u * 16u) {
+        if (k + 16u <= len) *reinterpret_cast<v4u32_un *>(dst + k) = *reinterpret_cast<const v4u32_un *>(src + k);
+        else for (uint32_t t = k; t < len; ++t) dst[t] = src[t];
+    }
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------
 struct PerFile {
     char *h_text = nullptr;                            // page-locked staging (+ 64 bytes: S1 reads whole 16-byte words)
@@ -859,6 +1009,12 @@ struct PerFile {
     uint32_t *d_cpos = nullptr, *d_cig_tile = nullptr, *d_cig_ops = nullptr;
     uint8_t *d_cig_cnt = nullptr;
     uint64_t ops_cap = 0;
+    // xm_strip_set_refs: the file's reference names and their table (a copy per slot), and per record what E1 leaves for E2
+    uint8_t *d_ref_names = nullptr;
+    uint32_t *d_ref_at = nullptr, *d_ref_table = nullptr, ref_mask = 0, n_refs = 0;
+    bool refs_set = false;
+    uint32_t *d_esize = nullptr, *d_eseq = nullptr, *d_elseq = nullptr;
+    uint64_t enc_records = 0;
 };
 
 struct Slot : ClassifyOut, GatherPlan {               // (xm_slot.h: the columns and the classify outputs; the gather's per-unit arrays)
@@ -875,6 +1031,14 @@ struct Slot : ClassifyOut, GatherPlan {               // (xm_slot.h: the columns
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_filled = nullptr, ev_out = nullptr;
     bool out_issued = false;
+    // xm_strip_fetch_bins_bam: the records without frames, the members' descriptors, CRCs and layout, the first declined line
+    uint8_t *d_pay = nullptr;
+    uint64_t pay_cap = 0;
+    xm_bgzf_block *d_members = nullptr;
+    uint32_t *d_member_crc = nullptr;
+    BamLayout *d_layout = nullptr;
+    uint64_t member_cap = 0;
+    unsigned long long *d_declined = nullptr, *h_declined = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     uint64_t uploaded[2] = {0, 0};                     // bytes of the staged windows already on their way (xm_strip_upload)
@@ -905,7 +1069,13 @@ void free_slot(Slot &sl)
         hfree(q.h_loff); hfree(q.h_llen); hfree(q.h_nlen); hfree(q.h_lflag);
         dfree(q.d_nm); dfree(q.d_cpos); dfree(q.d_cig_tile); dfree(q.d_cig_ops); dfree(q.d_cig_cnt);
         q.ops_cap = 0;
+        dfree(q.d_ref_names); dfree(q.d_ref_at); dfree(q.d_ref_table);
+        q.refs_set = false; q.n_refs = 0;
+        dfree(q.d_esize); dfree(q.d_eseq); dfree(q.d_elseq);
+        q.enc_records = 0;
     }
+    dfree(sl.d_pay); dfree(sl.d_members); dfree(sl.d_member_crc); dfree(sl.d_layout);
+    sl.pay_cap = sl.member_cap = 0;
     sl.release();
     sl.free_units();
     dfree(sl.d_out); hfree(sl.h_out);
@@ -1031,6 +1201,8 @@ int xm_strip_create(xm_ctx *ctx, int device_id, xm_strip **out)
         if (e == hipSuccess) e = sl.create();
         if (e == hipSuccess) e = hipMalloc((void **)&sl.d_gstate, 16 * sizeof(uint32_t));
         if (e == hipSuccess) e = xmpin::host_malloc((void **)&sl.h_gstate, 16 * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_declined, 2 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = xmpin::host_malloc((void **)&sl.h_declined, 2 * sizeof(unsigned long long));
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.ev_filled, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.ev_out, hipEventBlockingSync | hipEventDisableTiming);
     }
@@ -1064,6 +1236,7 @@ int xm_strip_destroy(xm_strip *s)
         sl.destroy();
         dfree(sl.d_state); dfree(sl.d_summary); hfree(sl.h_summary);
         dfree(sl.d_gstate); hfree(sl.h_gstate);
+        dfree(sl.d_declined); hfree(sl.h_declined);
         if (sl.ev_filled) (void)hipEventDestroy(sl.ev_filled);
         if (sl.ev_out) (void)hipEventDestroy(sl.ev_out);
         if (k == XMS_SLOTS - 1 && sl.copy_stream) (void)hipStreamDestroy(sl.copy_stream);    // shared by the slots: once, behind all
@@ -1313,6 +1486,144 @@ int xm_strip_fetch_bins(xm_strip *s, int slot, uint64_t n_records, int paired, u
         a.d_text, b.d_text, a.d_loff, b.d_loff, a.d_llen, b.d_llen, sl.d_idx, d_off, n_units, n, paired ? 1 : 0, sink_mask, sl.d_usize, sl.d_uplace,
         sl.d_out, (uint32_t)sl.out_cap);
     const int rc = Slot::send_home(s, st, sl.copy_stream, sl.ev_filled, sl.ev_out, sl.d_out, sl.h_out, at.total);
+    sl.out_issued = true;
+    return rc;
+}
+
+int xm_strip_set_refs(xm_strip *s, int file, const uint8_t *names, const uint32_t *at, uint32_t n_refs)
+{
+    if (!s || file < 0 || file > 1 || (n_refs && (!names || !at))) return XM_ERR_INVALID_ARG;
+    for (uint32_t k = 0; k < n_refs; ++k)
+        if (at[k + 1] < at[k]) return XM_ERR_INVALID_ARG;
+    std::vector<uint32_t> table;
+    uint32_t mask = 0;
+    try {
+        if (!xmsam::build_ref_table(names, at, n_refs, table, mask)) return XM_ERR_INVALID_ARG;       // a name twice
+    } catch (const std::bad_alloc &) {
+        return XM_ERR_OOM;
+    }
+    XMF_HIP(s, hipSetDevice(s->device));
+    XMF_HIP(s, hipDeviceSynchronize());
+    const uint32_t zero = 0;
+    for (int slot = 0; slot < XMS_SLOTS; ++slot) {                          // a copy per slot: the slots' streams share nothing
+        PerFile &q = s->slot[slot].pf[file];
+        q.refs_set = false;
+        q.n_refs = 0;
+        const size_t bytes = n_refs ? at[n_refs] : 0;
+        XMF_TRY(dalloc(s, q.d_ref_names, bytes + 16)); XMF_TRY(dalloc(s, q.d_ref_at, (size_t)n_refs + 1)); XMF_TRY(dalloc(s, q.d_ref_table, table.size()));
+        if (bytes) XMF_HIP(s, hipMemcpy(q.d_ref_names, names, bytes, hipMemcpyHostToDevice));
+        XMF_HIP(s, hipMemcpy(q.d_ref_at, n_refs ? at : &zero, ((size_t)n_refs + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+        XMF_HIP(s, hipMemcpy(q.d_ref_table, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        q.ref_mask = mask;
+        q.n_refs = n_refs;
+        q.refs_set = true;
+    }
+    return XM_OK;
+}
+
+int xm_strip_fetch_bins_bam(xm_strip *s, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload,
+                            int32_t ref_shift, xm_strip_bam_bins *out)
+{
+    if (!s || slot < 0 || slot >= XMS_SLOTS || !out) return XM_ERR_INVALID_ARG;
+    Slot &sl = s->slot[slot];
+    if (n_records > sl.record_cap || n_records > 0xFFFFFFF0ull || sl.last_score_mode < 0 || !sl.classified) return XM_ERR_INVALID_ARG;
+    const uint32_t P = block_payload ? block_payload : 65280u;
+    if (P < 64u || P > 65280u) return XM_ERR_INVALID_ARG;
+    // the references of every file a sink takes lines of (bins 0, 2, 5: file 1; 1, 3: file 2; 4: both)
+    if (((sink_mask & 0x35u) && !sl.pf[0].refs_set) || ((sink_mask & 0x1Au) && !sl.pf[1].refs_set)) return XM_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    const uint32_t n = (uint32_t)n_records;
+    const uint64_t units64 = sl.h_off_counts[7];
+    if (n == 0 || units64 == 0) return XM_OK;
+    if (units64 > n_records) return XM_ERR_INVALID_ARG;
+    const uint32_t n_units = (uint32_t)units64;
+    XMF_HIP(s, hipSetDevice(s->device));
+    const uint64_t want_cap = std::min<uint64_t>(2 * sl.window_cap + 4096, 0xFFFFFFF0ull);     // (xm_strip_fetch_bins' stream: shared)
+    if (sl.out_cap < want_cap) {
+        XMF_HIP(s, hipStreamSynchronize(sl.copy_stream));
+        sl.out_cap = 0;
+        XMF_TRY(dalloc(s, sl.d_out, (size_t)want_cap + 64)); XMF_TRY(halloc(s, sl.h_out, (size_t)want_cap + 64));
+        sl.out_cap = want_cap;
+    }
+    if (sl.pay_cap < sl.out_cap) {
+        sl.pay_cap = 0;
+        XMF_TRY(dalloc(s, sl.d_pay, (size_t)sl.out_cap + 64));
+        sl.pay_cap = sl.out_cap;
+    }
+    for (int f = 0; f < 2; ++f) {
+        PerFile &q = sl.pf[f];
+        if (q.enc_records < sl.record_cap) {
+            q.enc_records = 0;
+            const size_t cnt = (size_t)sl.record_cap + 64;
+            XMF_TRY(dalloc(s, q.d_esize, cnt)); XMF_TRY(dalloc(s, q.d_eseq, cnt)); XMF_TRY(dalloc(s, q.d_elseq, cnt));
+            q.enc_records = sl.record_cap;
+        }
+    }
+    XMF_TRY(sl.reserve_units(s, sl.record_cap));
+    out->text = sl.h_out;
+    hipStream_t st = sl.stream;
+    if (sl.out_issued) XMF_HIP(s, hipStreamWaitEvent(st, sl.ev_out, 0));            // the previous window's stream has left d_out
+    const unsigned long long *d_off = reinterpret_cast<const unsigned long long *>(sl.d_off_counts);
+    EncFile ef[2];
+    for (int f = 0; f < 2; ++f) {
+        const PerFile &q = sl.pf[f];
+        ef[f].text = q.d_text; ef[f].loff = q.d_loff; ef[f].llen = q.d_llen; ef[f].lflag = q.d_lflag;
+        ef[f].refs = xmsam::RefHash{q.d_ref_names, q.d_ref_at, q.d_ref_table, q.ref_mask, q.refs_set ? q.n_refs : 0u};
+        ef[f].esize = q.d_esize; ef[f].eseq = q.d_eseq; ef[f].elseq = q.d_elseq;
+    }
+    const uint32_t per = paired ? 4u : 2u;
+    const uint64_t lines64 = (uint64_t)n_units * per;
+    if (lines64 > 0xFFFFFF00ull) { out->status = 2; return XM_OK; }
+    XMF_HIP(s, hipMemsetAsync(sl.d_gstate + GS_FLAG, 0, GS_LIVE_BYTES, st));
+    XMF_HIP(s, hipMemsetAsync(sl.d_declined, 0xFF, sizeof(unsigned long long), st));
+    sam_enc_size_kernel<<<(uint32_t)((lines64 + 255u) / 256u), 256, 0, st>>>(ef[0], ef[1], sl.d_idx, d_off, n_units, n, paired ? 1 : 0, sink_mask, sl.d_usize,
+                                                                             reinterpret_cast<unsigned long long *>(sl.d_gstate + GS_TOTAL64),
+                                                                             sl.d_gstate + GS_FLAG, sl.d_declined);
+    XMF_HIP(s, hipMemcpyAsync(sl.h_declined, sl.d_declined, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    Placed at;
+    XMF_TRY(sl.place_units(s, st, n_units, d_off, sl.d_gstate, sl.h_gstate, nullptr, at));
+    if (at.flag != 0u) { out->status = 3; return XM_OK; }                   // a line that is not '\t'.join(fields): the host's window
+    if (*sl.h_declined != ~0ull) {                                            // a line the device does not encode: the host's window
+        const unsigned long long key = *sl.h_declined;
+        const uint64_t p = key >> 10;
+        if (p >= n_units) return XM_ERR_HIP;
+        const uint32_t i = sl.h_idx[p];
+        out->status = 1;
+        out->reason = (int32_t)(key & 0xFFu);
+        out->declined_file = (int32_t)((key >> 9) & 1u);
+        out->declined_record = paired ? (uint64_t)i - 1u + ((key >> 8) & 1u) : (uint64_t)i;
+        return XM_OK;
+    }
+    if (at.total > sl.pay_cap) { out->status = 2; return XM_OK; }
+    // the framed layout, as bam_layout_kernel derives it on the device: the same sums in 64 bits, against the capacity, before anything is written
+    uint64_t framed = 0, n_members = 0;
+    for (int k = 0; k < 7; ++k) {
+        out->bin_off[k] = framed;
+        if (at.starts[k + 1] < at.starts[k]) return XM_ERR_HIP;
+        const uint64_t len = at.starts[k + 1] - at.starts[k], members = (len + P - 1u) / P;
+        framed += len + members * BGZF_FRAME;
+        n_members += members;
+    }
+    out->bin_off[7] = framed;
+    if (framed > sl.out_cap) { std::memset(out->bin_off, 0, sizeof out->bin_off); out->status = 2; return XM_OK; }
+    if (n_members == 0) return XM_OK;
+    if (sl.member_cap < n_members) {                                        // (the slot's stream is idle: place_units waited)
+        sl.member_cap = 0;
+        const size_t cnt = (size_t)n_members + n_members / 4 + 64;
+        XMF_TRY(dalloc(s, sl.d_members, cnt)); XMF_TRY(dalloc(s, sl.d_member_crc, cnt));
+        if (!sl.d_layout) XMF_TRY(dalloc(s, sl.d_layout, 1));
+        sl.member_cap = cnt;
+    }
+    const uint32_t nm = (uint32_t)n_members;
+    sam_enc_write_kernel<<<(uint32_t)((lines64 + 3u) / 4u), 256, 0, st>>>(ef[0], ef[1], sl.d_idx, d_off, n_units, n, paired ? 1 : 0, sink_mask, sl.d_usize,
+                                                                          sl.d_uplace, ref_shift, sl.d_pay, (uint32_t)sl.pay_cap);
+    bam_layout_kernel<<<(nm + 255u) / 256u, 256, 0, st>>>(sl.d_gstate + GS_STARTS, P, nm, sl.d_layout, sl.d_members);
+    sam_enc_frame_copy_kernel<<<nm, 256, 0, st>>>(sl.d_pay, (uint32_t)at.total, sl.d_gstate + GS_STARTS, sl.d_layout, sl.d_members, nm, P, sl.d_out,
+                                                  (uint32_t)sl.out_cap);
+    const int rc_crc = xm_bgzf_crc32_dev(s->ctx, st, sl.d_out, sl.d_members, n_members, sl.d_member_crc);
+    if (rc_crc != XM_OK) { take_ctx_error(s); return rc_crc; }
+    bam_frame_kernel<<<(nm + 255u) / 256u, 256, 0, st>>>(sl.d_members, sl.d_member_crc, nm, sl.d_out, (uint32_t)sl.out_cap);
+    const int rc = Slot::send_home(s, st, sl.copy_stream, sl.ev_filled, sl.ev_out, sl.d_out, sl.h_out, framed);
     sl.out_issued = true;
     return rc;
 }
