@@ -142,10 +142,23 @@ __device__ __forceinline__ uint32_t lane_value(uint32_t v, int lane)
 
 // This wave's LDS operations so far have been performed (LDS executes a wave's operations in issue order), and the
 // compiler moves no memory access across this point.
+#ifdef XM_LOCKSTEP_HOST
+// the host build of tests/lockstep: a rendezvous of the wave's lanes, which carries the caller's line
+__device__ __forceinline__ void lds_settle(int line = __builtin_LINE()) { ls::settle(line); }
+#else
 __device__ __forceinline__ void lds_settle()
 {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
+#endif
+
+// Every launch of this file.  XM_LOCKSTEP_HOST is defined by the host programs of tests/lockstep only, which execute the
+// kernel lane by lane on the CPU with the geometry the launchers below compute.
+#ifdef XM_LOCKSTEP_HOST
+#define XM_LAUNCH(kernel, grid, block, st, ...) do { (void)(st); ls::launch(grid, block, [&] { kernel(__VA_ARGS__); }); } while (0)
+#else
+#define XM_LAUNCH(kernel, grid, block, st, ...) kernel<<<grid, block, 0, st>>>(__VA_ARGS__)
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // Counting (category_counts + the per-granule bin counts the stable split needs), shared by K1 (fused: the
@@ -1968,7 +1981,7 @@ void launch_stream_probe(hipStream_t st, uint64_t n, const int32_t *c0, const in
     const uint64_t n_groups = n / 4;
     const uint32_t grid = (uint32_t)((n_groups + XM_CLASSIFY_BLOCK - 1) / XM_CLASSIFY_BLOCK);
     if (grid == 0) return;
-    stream_probe_kernel<<<grid, XM_CLASSIFY_BLOCK, 0, st>>>(reinterpret_cast<const v4i32 *>(c0), reinterpret_cast<const v4i32 *>(c1),
+    XM_LAUNCH(stream_probe_kernel, grid, XM_CLASSIFY_BLOCK, st, reinterpret_cast<const v4i32 *>(c0), reinterpret_cast<const v4i32 *>(c1),
                                                             reinterpret_cast<const v4i32 *>(c2), reinterpret_cast<const v4i32 *>(c3),
                                                             reinterpret_cast<uint16_t *>(out), n_groups);
 }
@@ -2012,7 +2025,7 @@ void launch_classify(hipStream_t st, int mode, uint64_t n, const T *as1, const T
     const uint8_t *bits8 = reinterpret_cast<const uint8_t *>(unit_bits);
     const CountSink sink = make_sink(cp, mode);
     const bool paired = mode != XM_MODE_SE;
-#define XM_LAUNCH_CLS(P, C, B) classify_kernel<T, P, XM_CLASSIFY_NT, XM_CLASSIFY_BLOCK, C, B><<<grid, XM_CLASSIFY_BLOCK, 0, st>>>(as1, xs1, as2, xs2, bits8, m, code, n, sink)
+#define XM_LAUNCH_CLS(P, C, B) XM_LAUNCH((classify_kernel<T, P, XM_CLASSIFY_NT, XM_CLASSIFY_BLOCK, C, B>), grid, XM_CLASSIFY_BLOCK, st, as1, xs1, as2, xs2, bits8, m, code, n, sink)
     if (cp && cp->bins4) {
         if (mode == XM_MODE_SE) XM_LAUNCH_CLS(false, true, XM_MODE_SE);
         else if (mode == XM_MODE_PE_LIBERAL) XM_LAUNCH_CLS(true, true, XM_MODE_PE_LIBERAL);
@@ -2039,7 +2052,7 @@ void launch_classify_runs(hipStream_t st, int mode, uint64_t n, const T *as1, co
     rs.runs16 = ro.runs16;
     rs.gran_counts16 = ro.gran_counts16;
     rs.counts_rep = reinterpret_cast<unsigned long long *>(ro.counts_rep);
-#define XM_LAUNCH_RUNS(P, B) classify_runs_kernel<T, P, XM_CLASSIFY_NT, XM_CLASSIFY_BLOCK, B><<<grid, XM_CLASSIFY_BLOCK, 0, st>>>(as1, xs1, as2, xs2, bits8, m, n, rs)
+#define XM_LAUNCH_RUNS(P, B) XM_LAUNCH((classify_runs_kernel<T, P, XM_CLASSIFY_NT, XM_CLASSIFY_BLOCK, B>), grid, XM_CLASSIFY_BLOCK, st, as1, xs1, as2, xs2, bits8, m, n, rs)
     if (mode == XM_MODE_SE) XM_LAUNCH_RUNS(false, XM_MODE_SE);
     else if (mode == XM_MODE_PE_LIBERAL) XM_LAUNCH_RUNS(true, XM_MODE_PE_LIBERAL);
     else XM_LAUNCH_RUNS(true, XM_MODE_PE_CONSERVATIVE);
@@ -2053,7 +2066,7 @@ template void launch_classify_runs<double>(hipStream_t, int, uint64_t, const dou
 
 void launch_runs_finish(hipStream_t st, int mode, uint64_t *counts_rep, uint64_t *counts, uint64_t *n_out)
 {
-    runs_finish_kernel<<<1, 256, 0, st>>>(reinterpret_cast<unsigned long long *>(counts_rep),
+    XM_LAUNCH(runs_finish_kernel, 1, 256, st, reinterpret_cast<unsigned long long *>(counts_rep),
                                           reinterpret_cast<unsigned long long *>(counts),
                                           reinterpret_cast<unsigned long long *>(n_out), mode);
 }
@@ -2067,11 +2080,9 @@ void launch_classify_cigar(hipStream_t st, int mode, uint64_t n,
     const uint32_t grid = (uint32_t)((n + per_block - 1) / per_block);
     const uint8_t *bits8 = reinterpret_cast<const uint8_t *>(unit_bits);
     if (mode == XM_MODE_SE)
-        classify_cigar_kernel<false, XM_CIGAR_BLOCK><<<grid, XM_CIGAR_BLOCK, 0, st>>>(
-            nm1, off1, ops1, xs1, nm2, off2, ops2, xs2, bits8, m, code, n, range_flag);
+        XM_LAUNCH((classify_cigar_kernel<false, XM_CIGAR_BLOCK>), grid, XM_CIGAR_BLOCK, st, nm1, off1, ops1, xs1, nm2, off2, ops2, xs2, bits8, m, code, n, range_flag);
     else
-        classify_cigar_kernel<true, XM_CIGAR_BLOCK><<<grid, XM_CIGAR_BLOCK, 0, st>>>(
-            nm1, off1, ops1, xs1, nm2, off2, ops2, xs2, bits8, m, code, n, range_flag);
+        XM_LAUNCH((classify_cigar_kernel<true, XM_CIGAR_BLOCK>), grid, XM_CIGAR_BLOCK, st, nm1, off1, ops1, xs1, nm2, off2, ops2, xs2, bits8, m, code, n, range_flag);
 }
 
 void launch_classify_cigp(hipStream_t st, int mode, uint64_t n, const CigCols &s1, const CigCols &s2,
@@ -2082,7 +2093,7 @@ void launch_classify_cigp(hipStream_t st, int mode, uint64_t n, const CigCols &s
     const uint32_t n_tiles = (uint32_t)((n + 255) / 256);
     const uint8_t *bits8 = reinterpret_cast<const uint8_t *>(unit_bits);
     const CountSink sink = make_sink(&cp, mode);
-#define XM_LAUNCH_CIGP(P, B) classify_cigp_kernel<P, XM_CIGP_BLOCK, true, B><<<grid, XM_CIGP_BLOCK, 0, st>>>(s1, s2, bits8, m, code, n, n_tiles, range_flag, sink)
+#define XM_LAUNCH_CIGP(P, B) XM_LAUNCH((classify_cigp_kernel<P, XM_CIGP_BLOCK, true, B>), grid, XM_CIGP_BLOCK, st, s1, s2, bits8, m, code, n, n_tiles, range_flag, sink)
     if (cp.bins4) {
         if (mode == XM_MODE_SE) XM_LAUNCH_CIGP(false, XM_MODE_SE);
         else if (mode == XM_MODE_PE_LIBERAL) XM_LAUNCH_CIGP(true, XM_MODE_PE_LIBERAL);
@@ -2096,7 +2107,7 @@ void launch_classify_cigp(hipStream_t st, int mode, uint64_t n, const CigCols &s
 void launch_hist(hipStream_t st, int mode, uint64_t n, const uint8_t *code, const CountPlan &cp)
 {
     const uint32_t grid = (cp.plan.n_gran + (XM_BLOCK / 64) - 1) / (XM_BLOCK / 64);
-    hist_kernel<<<grid, XM_BLOCK, 0, st>>>(code, n, cp.plan.n_gran, make_sink(&cp, mode));
+    XM_LAUNCH(hist_kernel, grid, XM_BLOCK, st, code, n, cp.plan.n_gran, make_sink(&cp, mode));
 }
 
 void launch_scan(hipStream_t st, const CountPlan &cp, uint32_t *gran_off, uint64_t *bin_totals, uint64_t *counts)
@@ -2108,7 +2119,7 @@ void launch_scan(hipStream_t st, const CountPlan &cp, uint32_t *gran_off, uint64
     // a chunk [gran0, gran1) begins at a part boundary; the scan sees the granules up to the chunk's end
     const uint32_t part0 = cp.gran1 ? cp.gran0 / XM_PART_GRAN : 0u;
     const uint32_t part1 = cp.gran1 ? (cp.gran1 + XM_PART_GRAN - 1) / XM_PART_GRAN : n_parts;
-    scan_kernel<<<dim3(part1 - part0, 8), XM_SCAN_THREADS, 0, st>>>(cp.gran_counts, cp.gran1 ? cp.gran1 : cp.plan.n_gran, cp.plan.gran_stride,
+    XM_LAUNCH(scan_kernel, dim3(part1 - part0, 8), XM_SCAN_THREADS, st, cp.gran_counts, cp.gran1 ? cp.gran1 : cp.plan.n_gran, cp.plan.gran_stride,
                                                                    cp.part_tot, gran_off, bt, rep, cnt, part0, n_parts);
 }
 
@@ -2139,7 +2150,7 @@ void launch_scatter(hipStream_t st, const GranPlan &p, int mode, uint64_t n, con
     const bool wide = n > (1ull << 30);                 // unit positions * 4 bytes may pass 2^32
     const bool stage = mode == XM_MODE_SE;
     const ListOut lo = lists ? *lists : ListOut{{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 0u};
-#define XM_LAUNCH_SCT(W, NIB, STG, L, M) scatter_kernel<XM_GRAN / 256, W, NIB, STG, L, M><<<grid, XM_BLOCK, 0, st>>>(code, n, mode, g_end, p.gran_stride, gran_counts, gran_off, bt, bo, idx_out, part_tot, lo, gran_per_wave, g_first, last)
+#define XM_LAUNCH_SCT(W, NIB, STG, L, M) XM_LAUNCH((scatter_kernel<XM_GRAN / 256, W, NIB, STG, L, M>), grid, XM_BLOCK, st, code, n, mode, g_end, p.gran_stride, gran_counts, gran_off, bt, bo, idx_out, part_tot, lo, gran_per_wave, g_first, last)
 #define XM_LAUNCH_SCT0(W, NIB, STG, L) do { if (multi) XM_LAUNCH_SCT(W, NIB, STG, L, true); else XM_LAUNCH_SCT(W, NIB, STG, L, false); } while (0)
 #define XM_LAUNCH_SCT1(W, NIB, STG) do { if (lists) XM_LAUNCH_SCT0(W, NIB, STG, true); else XM_LAUNCH_SCT0(W, NIB, STG, false); } while (0)
 #define XM_LAUNCH_SCT2(W, NIB) do { if (stage) XM_LAUNCH_SCT1(W, NIB, true); else XM_LAUNCH_SCT1(W, NIB, false); } while (0)
@@ -2154,7 +2165,7 @@ void launch_scatter(hipStream_t st, const GranPlan &p, int mode, uint64_t n, con
 void launch_mate_correlate(hipStream_t st, uint64_t n, const double *track, uint32_t m, const double *density, double *out)
 {
     const uint32_t grid = (uint32_t)((n + XM_CORR_T - 1) / XM_CORR_T);
-    mate_correlate_kernel<<<grid, XM_CORR_T, 0, st>>>(track, n, density, m, out);
+    XM_LAUNCH(mate_correlate_kernel, grid, XM_CORR_T, st, track, n, density, m, out);
 }
 
 void launch_cigar(hipStream_t st, uint32_t max_blocks, uint64_t n, const int32_t *nm, const uint32_t *cig_off,
@@ -2163,7 +2174,7 @@ void launch_cigar(hipStream_t st, uint32_t max_blocks, uint64_t n, const int32_t
     uint64_t blocks = (n + XM_BLOCK - 1) / XM_BLOCK;
     if (blocks > max_blocks) blocks = max_blocks;
     if (blocks == 0) blocks = 1;
-    cigar_kernel<<<(uint32_t)blocks, XM_BLOCK, 0, st>>>(n, nm, cig_off, cig_oplen, as_out, range_flag);
+    XM_LAUNCH(cigar_kernel, (uint32_t)blocks, XM_BLOCK, st, n, nm, cig_off, cig_oplen, as_out, range_flag);
 }
 
 }  // namespace xm
