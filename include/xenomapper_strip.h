@@ -18,9 +18,10 @@
  *
  * Scope: SAM text, all three built-in plugins, the walk with and without --skip_repeated_reads (xenomapper.py:110-117).
  * Windows are shorter than 4 GiB - 64 KiB.  BAM input, windows beyond that and non-ASCII text stay with xenomapper_host.h.
- * The six outputs come back as text (xm_strip_fetch_bins) or as BAM (xm_strip_fetch_bins_bam: every wanted line encoded as a BAM
- * alignment record on the device, in BGZF members of stored blocks).  The BAM header made from the @SQ lines, compressed members and
- * the file path behind classify_sam_files are not part of this interface yet: the caller supplies the reference names.
+ * The six outputs come back as text (xm_strip_fetch_bins) or as BAM: every wanted line encoded as a BAM alignment record on the
+ * device, in BGZF members of stored blocks (xm_strip_fetch_bins_bam) or of deflated ones (xm_strip_fetch_bins_bamz).  The BAM header
+ * made from the @SQ lines is the caller's, who also supplies the reference names (xm_strip_set_refs); the file path behind
+ * classify_sam_files(encode_sam=True) does both and sends the windows the device declines through xmh_sam_encode.
  *
  * A stripper has two slots so that one window pair can be copied, uploaded and stripped (one host thread) while
  * the block before it is classified and written (another thread); calls on one slot must not overlap.
@@ -36,7 +37,7 @@ extern "C" {
 
 #define XMS_ABI_VERSION 4   /* 2: xm_strip_fetch_bins / xm_strip_out_wait.  3: two calls for reading a window ahead (begun behind
                                a gap, its lead set later).  4: those two withdrawn -- reading ahead measured no better.  Additive since,
-                               the version unchanged: xm_strip_set_refs / xm_strip_fetch_bins_bam */
+                               the version unchanged: xm_strip_set_refs / xm_strip_fetch_bins_bam, then xm_strip_fetch_bins_bamz */
 #define XMS_SLOTS 2
 #define XMS_MAX_WINDOW 0xFFFF0000ull
 
@@ -182,6 +183,19 @@ typedef struct {
 } xm_strip_bam_bins;
 int xm_strip_fetch_bins_bam(xm_strip *s, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload,
                             int32_t ref_shift, xm_strip_bam_bins *out);
+/*
+ * The same six outputs as ordinary, COMPRESSED BAM: arguments, result, records and their order per bin as xm_strip_fetch_bins_bam,
+ * status / reason / declined_* decided by the same rules at the same points, but every member holds what xm_bgzf_deflate_dev makes
+ * of its payload (xenomapper_bgzf.h).  Bin b's bytes = text[bin_off[b] .. bin_off[b + 1]) are exactly those of xm_bgzf_compress on the
+ * bin's records at block_payload, member for member; a bin without wanted units gets no member.  status 2 is decided by the stored
+ * call's sums (payload + 31 per member), which a deflated member never exceeds.  The call waits for the encoder -- the members'
+ * places are the scan of their lengths --: bin_off is final when it returns.  A member the encoder declines is XM_ERR_HIP
+ * (xm_strip_last_error).  The slot's first such call makes what only this route needs -- a place per member's stream, three words
+ * per member and the encoder's scratch (xm_bgzf_deflate_work_bytes()) --: XM_ERR_OOM when they cannot be made; xm_strip_destroy
+ * frees them.  xm_strip_fetch_bins_bam and xm_strip_fetch_bins may still follow on the same classified block, in either order.
+ */
+int xm_strip_fetch_bins_bamz(xm_strip *s, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload,
+                             int32_t ref_shift, xm_strip_bam_bins *out);
 
 /* Bring the first n_records of the slot's score columns and ceil(n/64) words of the unit mask to the host (for records
  * the caller must patch by the text rules).  Any pointer may be NULL. */

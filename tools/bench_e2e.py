@@ -2,6 +2,7 @@
 """End-to-end SAM -> six SAM files throughput of the file fast path (C++ stripper -> GPU -> C++ writer).
 
     python tools/bench_e2e.py --pairs 2000000 --threads 0
+    python tools/bench_e2e.py --pairs 2000000 --bam-out [--compress]      (six BAM files: the lines encoded on the GPU)
 
 Input: a synthetic 2x150 bp paired SAM text twin (50 k pairs, seed 2002) tiled to the requested size in
 /dev/shm.  Reports read-pairs/s including parsing, H2D/D2H through the host-buffer C ABI and writing all six
@@ -17,8 +18,10 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
-def run(pairs=2_000_000, threads=0, mode="liberal", workdir="/dev/shm", out_dir=None):
-    """One warm-up and one timed pass; returns the result record (also used by bench.py's `e2e.sam_text`)."""
+def run(pairs=2_000_000, threads=0, mode="liberal", workdir="/dev/shm", out_dir=None, out_format="sam", bam_compress=False):
+    """One warm-up and one timed pass; returns the result record (also used by bench.py's `e2e.sam_text`).
+    out_format="bam": the six outputs as BAM (classify_sam_files(output_format="bam", encode_sam=True); bam_compress: deflated members);
+    each pass writes the BAM headers first, outside the timed part, as the text run writes none."""
     from xenomapper_amd import _host, synth, xenomapper as xm
     base = 50_000
     t1, t2, _ = synth.sam_text_pair(n_pairs=base, seed=2002, profile="bowtie2", paired=mode != "se", read_len=150)
@@ -37,8 +40,10 @@ def run(pairs=2_000_000, threads=0, mode="liberal", workdir="/dev/shm", out_dir=
         paths.append(path)
     size = sum(os.path.getsize(p) for p in paths)
     names = ("primary_specific", "secondary_specific", "primary_multi", "secondary_multi", "unassigned", "unresolved")
-    out_paths = [os.path.join(out_dir, "xm_e2e_out_%s_%d.sam" % (k, os.getpid())) for k in names] if out_dir else []
-    sinks = {k: open(out_paths[i] if out_dir else os.devnull, "wt") for i, k in enumerate(names)}
+    as_bam = out_format == "bam"
+    out_paths = [os.path.join(out_dir, "xm_e2e_out_%s_%d.%s" % (k, os.getpid(), out_format)) for k in names] if out_dir else []
+    sinks = {k: open(out_paths[i] if out_dir else os.devnull, "wb" if as_bam else "wt") for i, k in enumerate(names)}
+    how = dict(output_format="bam", encode_sam=True, bam_compress=bool(bam_compress)) if as_bam else {}
     try:
         xm.default_context()
         for warm in (True, False):
@@ -46,18 +51,33 @@ def run(pairs=2_000_000, threads=0, mode="liberal", workdir="/dev/shm", out_dir=
                 if out_dir:
                     sink.seek(0)
                     sink.truncate()
+            head_bytes = 0
+            if as_bam:
+                with open(paths[0]) as f1, open(paths[1]) as f2:
+                    xm.process_headers(f1, f2, output_format="bam", encode_sam=True, **sinks)
+                for sink in sinks.values():
+                    sink.flush()
+                    head_bytes += sink.tell() if out_dir else 0
             t0 = time.perf_counter()
             counts = xm.classify_sam_files(paths[0], paths[1], paired=mode != "se", conservative=mode == "conservative",
-                                           n_threads=threads, **sinks)
+                                           n_threads=threads, **how, **sinks)
             for sink in sinks.values():
                 sink.flush()
             el = time.perf_counter() - t0
         units = sum(counts.values())
-        return {"metric": "end-to-end read-pairs/s (SAM text in, six SAM files out)", "value": units / el,
+        prof = xm.LAST_FILE_PROFILE
+        # bytes of the timed pass: the files' own sizes, or (to /dev/null) what the run counted -- BAM: every member and the six
+        # end-of-file markers, without the headers; text: the windows gathered on the device
+        if out_dir:
+            out_bytes = sum(os.path.getsize(p) for p in out_paths) - head_bytes
+        else:
+            out_bytes = int(prof.get("bam_out_bytes", 0)) + 28 * len(names) if as_bam else int(prof.get("sam_out_bytes", 0))
+        return {"metric": "end-to-end read-pairs/s (SAM text in, six %s files out)" % ("BAM" if as_bam else "SAM"), "value": units / el,
                 "units": units, "seconds": el, "input_bytes": size, "input_GBps": size / el / 1e9,
                 "threads": threads or _host.lib().xmh_default_threads(), "mode": mode,
                 "outputs": "files" if out_dir else "/dev/null",
                 "output_bytes": sum(os.path.getsize(p) for p in out_paths),
+                "out_format": ("bamz" if bam_compress else "bam") if as_bam else "sam", "out_bytes": out_bytes,
                 # wall seconds per phase of the timed pass: window + parse run in a helper thread beside classify + emit + write
                 "phases": {k: round(v, 4) for k, v in xm.LAST_FILE_PROFILE.items()}}
     finally:
@@ -182,12 +202,16 @@ def main():
     ap.add_argument("--mode", default="liberal", choices=("liberal", "conservative", "se"))
     ap.add_argument("--dir", default="/dev/shm")
     ap.add_argument("--out-dir", default=None, help="write the six outputs to real files here (default: /dev/null)")
+    ap.add_argument("--bam-out", action="store_true", help="write the six outputs as BAM (the lines encoded on the GPU)")
+    ap.add_argument("--compress", action="store_true", help="with --bam-out: deflated members (ordinary compressed BAM)")
     ap.add_argument("--ceilings", action="store_true", help="print the host-side ceilings of this box instead")
     a = ap.parse_args()
     if a.ceilings:
         print(json.dumps(host_ceilings(a.dir)))
         return
-    print(json.dumps(run(a.pairs, a.threads, a.mode, a.dir, a.out_dir)))
+    if a.compress and not a.bam_out:
+        ap.error("--compress needs --bam-out")
+    print(json.dumps(run(a.pairs, a.threads, a.mode, a.dir, a.out_dir, out_format="bam" if a.bam_out else "sam", bam_compress=a.compress)))
 
 
 if __name__ == "__main__":

@@ -149,6 +149,7 @@ def lib():
         "xm_strip_fetch_bins": ([P, I, U64, I, ctypes.c_uint32, P], I),
         "xm_strip_set_refs": ([P, I, P, P, ctypes.c_uint32], I),
         "xm_strip_fetch_bins_bam": ([P, I, U64, I, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, P], I),
+        "xm_strip_fetch_bins_bamz": ([P, I, U64, I, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, P], I),
         "xm_strip_out_wait": ([P, I], I),
         "xm_strip_columns": ([P, I, U64, P, P, P, P, P], I),
         "xm_strip_device_columns": ([P, I, P], I),
@@ -202,7 +203,7 @@ EXPORTED = ("xm_abi_version", "xm_strerror", "xm_last_hip_error", "xm_ctx_create
             "xm_comm_unique_id", "xm_comm_init", "xm_comm_destroy", "xm_comm_size", "xm_allreduce_counts",
             "xm_timing_enable", "xm_timing_select", "xm_timing_reset", "xm_timing_read",
             "xms_abi_version", "xm_strip_create", "xm_strip_destroy", "xm_strip_reserve", "xm_strip_staging", "xm_strip_upload", "xm_strip_run",
-            "xm_strip_classify", "xm_strip_fetch_bins", "xm_strip_set_refs", "xm_strip_fetch_bins_bam", "xm_strip_out_wait", "xm_strip_columns", "xm_strip_cigar_columns", "xm_strip_device_columns", "xm_strip_last_error",
+            "xm_strip_classify", "xm_strip_fetch_bins", "xm_strip_set_refs", "xm_strip_fetch_bins_bam", "xm_strip_fetch_bins_bamz", "xm_strip_out_wait", "xm_strip_columns", "xm_strip_cigar_columns", "xm_strip_device_columns", "xm_strip_last_error",
             "xm_bgzf_index", "xm_bgzf_index_prefix", "xm_bgzf_inflate_dev", "xm_bgzf_inflate_walk_dev", "xm_bgzf_crc32_dev", "xm_bgzf_strerror",
             "xm_bgzf_deflate_work_bytes", "xm_bgzf_deflate_dev", "xm_bgzf_compress",
             "xm_bamdev_create", "xm_bamdev_destroy", "xm_bamdev_reserve", "xm_bamdev_staging", "xm_bamdev_run", "xm_bamdev_raw_wait", "xm_bamdev_fetch_raw", "xm_bamdev_raw", "xm_bamdev_fetch_wanted", "xm_bamdev_fetch_text", "xm_bamdev_fetch_bins", "xm_bamdev_fetch_bins_bam", "xm_bamdev_fetch_bins_bamz", "xm_bamdev_set_refs", "xm_bamdev_upload", "xm_bamdev_classify",
@@ -1070,9 +1071,17 @@ class Stripper(_FrontEnd):
         BGZF members of stored blocks (valid after out_wait()).  status 1: declined = (record, file, XMS_ENC_* reason) of the
         first wanted line the device does not encode; 2: more bytes than the buffers hold; 3: a wanted line that is not
         '\\t'.join(fields) -- then this window is the host encoder's (_host.sam_encode)."""
+        return self._fetch_bam_bins("xm_strip_fetch_bins_bam", slot, n_records, paired, sink_mask, block_payload, ref_shift)
+
+    def fetch_bins_bamz(self, slot, n_records, paired, sink_mask, block_payload=0, ref_shift=0):
+        """fetch_bins_bam with every member deflated on the device (xm_strip_fetch_bins_bamz): ordinary compressed BAM, bin b's bytes
+        those of Context.bgzf_compress on its records.  Same arguments, same result, the same three ways to decline a window."""
+        return self._fetch_bam_bins("xm_strip_fetch_bins_bamz", slot, n_records, paired, sink_mask, block_payload, ref_shift)
+
+    def _fetch_bam_bins(self, symbol, slot, n_records, paired, sink_mask, block_payload, ref_shift):
         t = _StripBamBins()
-        self._check(self._L.xm_strip_fetch_bins_bam(self._h, int(slot), int(n_records), int(bool(paired)), int(sink_mask), int(block_payload),
-                                                    int(ref_shift), ctypes.byref(t)), "xm_strip_fetch_bins_bam")
+        self._check(getattr(self._L, symbol)(self._h, int(slot), int(n_records), int(bool(paired)), int(sink_mask), int(block_payload),
+                                             int(ref_shift), ctypes.byref(t)), symbol)
         declined = (int(t.declined_record), int(t.declined_file), int(t.reason)) if t.status == 1 else None
         return self._bins_result(t) + (declined,)
 

@@ -267,6 +267,13 @@ def ref_blob(names):
     return blob, at
 
 
+# *reason of xmh_sam_encode by name (include/xenomapper_host.h)
+SAM_ENC_REASONS = {1: "XMH_ENC_FIELDS", 2: "XMH_ENC_QNAME", 3: "XMH_ENC_FLAG", 4: "XMH_ENC_RNAME", 5: "XMH_ENC_POS", 6: "XMH_ENC_MAPQ",
+                   7: "XMH_ENC_CIGAR", 8: "XMH_ENC_RNEXT", 9: "XMH_ENC_PNEXT", 10: "XMH_ENC_TLEN", 11: "XMH_ENC_SEQ", 12: "XMH_ENC_QUAL",
+                   13: "XMH_ENC_AUX", 14: "XMH_ENC_AUX_RANGE", 15: "XMH_ENC_SIZE", 32: "XMH_ENC_HOST_FLOAT",
+                   33: "XMH_ENC_HOST_LONG_CIGAR", 34: "XMH_ENC_HOST_SEQ_CODE", 35: "XMH_ENC_HOST_NUMBER"}
+
+
 def sam_encode(text, line_off, line_len, names, ref_shift=0, device_forms=False):
     """xmh_sam_encode: the lines text[line_off[i] : line_off[i] + line_len[i]] (text: uint8 array or bytes) as BAM alignment records
     -> (records back to back as bytes, sizes uint32[k], bad_line or None, reason).  With a bad line, k = bad_line: the records in

@@ -1,6 +1,6 @@
 // xm_bgzf_pack.h -- the kernel that makes complete BGZF members of deflated streams, for the two places that frame what
-// xm_bgzf_deflate_dev wrote: xm_bgzf_compress (xm_deflate.hip) and xm_bamdev_fetch_bins_bamz (xm_bamdev.hip).  In an anonymous
-// namespace like xm_gather.h: each translation unit that includes this gets its own.
+// xm_bgzf_deflate_dev wrote: xm_bgzf_compress (xm_deflate.hip), xm_bamdev_fetch_bins_bamz (xm_bamdev.hip) and xm_strip_fetch_bins_bamz
+// (xm_strip.hip).  In an anonymous namespace like xm_gather.h: each translation unit that includes this gets its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

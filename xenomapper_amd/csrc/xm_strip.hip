@@ -36,6 +36,8 @@
 #include <vector>
 
 #include "xm_bamframe.h"
+#include "xm_bamz.h"                     // the compressed route's descriptors and place scan
+#include "xm_bgzf_pack.h"                // bgzf_pack_kernel
 #include "xm_samrec.h"
 #include "xm_slot.h"
 
@@ -1039,6 +1041,12 @@ struct Slot : ClassifyOut, GatherPlan {               // (xm_slot.h: the columns
     BamLayout *d_layout = nullptr;
     uint64_t member_cap = 0;
     unsigned long long *d_declined = nullptr, *h_declined = nullptr;
+    // xm_strip_fetch_bins_bamz, made when the first such call comes: a place per member's stream, the streams' lengths, status and
+    // places, the encoder's scratch (placed: 8 bin starts and the status word)
+    uint8_t *d_zcomp = nullptr, *d_zwork = nullptr;
+    uint32_t *d_zclen = nullptr, *d_zstatus = nullptr;
+    unsigned long long *d_zoff = nullptr, *d_zplaced = nullptr, *h_zplaced = nullptr;
+    uint64_t z_comp_bytes = 0, z_member_cap = 0, z_work_bytes = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     uint64_t uploaded[2] = {0, 0};                     // bytes of the staged windows already on their way (xm_strip_upload)
@@ -1076,6 +1084,8 @@ void free_slot(Slot &sl)
     }
     dfree(sl.d_pay); dfree(sl.d_members); dfree(sl.d_member_crc); dfree(sl.d_layout);
     sl.pay_cap = sl.member_cap = 0;
+    dfree(sl.d_zcomp); dfree(sl.d_zwork); dfree(sl.d_zclen); dfree(sl.d_zstatus); dfree(sl.d_zoff); dfree(sl.d_zplaced); hfree(sl.h_zplaced);
+    sl.z_comp_bytes = sl.z_member_cap = sl.z_work_bytes = 0;
     sl.release();
     sl.free_units();
     dfree(sl.d_out); hfree(sl.h_out);
@@ -1172,6 +1182,36 @@ int mark_range(xm_strip *s, Slot &sl, int file, uint64_t len, uint64_t usable, u
     mark_kernel<<<a.n_chunks, SB, 0, sl.stream>>>(a);
     return XM_OK;
 }
+
+// what only the compressed BAM route needs, for n_members streams of `slot` bytes each; the slot's stream is idle.  A buffer that
+// cannot be made leaves its capacity at 0 (the next call tries again) and the error is the allocator's: XM_ERR_OOM.
+int ensure_bamz(xm_strip *s, Slot &sl, uint64_t n_members, uint64_t slot)
+{
+    if (sl.z_comp_bytes < n_members * slot) {
+        sl.z_comp_bytes = 0;
+        const uint64_t bytes = n_members * slot + n_members * slot / 4 + 64;
+        XMF_TRY(dalloc(s, sl.d_zcomp, (size_t)bytes));
+        sl.z_comp_bytes = bytes;
+    }
+    if (sl.z_member_cap < n_members) {
+        sl.z_member_cap = 0;
+        const size_t cap = (size_t)n_members + (size_t)n_members / 4 + 64;
+        XMF_TRY(dalloc(s, sl.d_zclen, cap)); XMF_TRY(dalloc(s, sl.d_zstatus, cap)); XMF_TRY(dalloc(s, sl.d_zoff, cap));
+        sl.z_member_cap = cap;
+    }
+    if (!sl.d_zplaced) XMF_TRY(dalloc(s, sl.d_zplaced, 16));
+    if (!sl.h_zplaced) XMF_TRY(halloc(s, sl.h_zplaced, 16));
+    if (sl.z_work_bytes == 0) {
+        XMF_TRY(dalloc(s, sl.d_zwork, (size_t)xm_bgzf_deflate_work_bytes()));
+        sl.z_work_bytes = xm_bgzf_deflate_work_bytes();
+    }
+    return XM_OK;
+}
+
+// xm_strip_fetch_bins_bam (deflated = false) and xm_strip_fetch_bins_bamz (true): one body, so that the arguments, the sizes and the
+// three ways a window is declined are decided by the same lines, before anything is written
+int fetch_bins_bam(xm_strip *s, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload, int32_t ref_shift,
+                   bool deflated, xm_strip_bam_bins *out);
 
 }  // namespace
 
@@ -1524,6 +1564,22 @@ int xm_strip_set_refs(xm_strip *s, int file, const uint8_t *names, const uint32_
 int xm_strip_fetch_bins_bam(xm_strip *s, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload,
                             int32_t ref_shift, xm_strip_bam_bins *out)
 {
+    return fetch_bins_bam(s, slot, n_records, paired, sink_mask, block_payload, ref_shift, false, out);
+}
+
+int xm_strip_fetch_bins_bamz(xm_strip *s, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload,
+                             int32_t ref_shift, xm_strip_bam_bins *out)
+{
+    return fetch_bins_bam(s, slot, n_records, paired, sink_mask, block_payload, ref_shift, true, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+int fetch_bins_bam(xm_strip *s, int slot, uint64_t n_records, int paired, uint32_t sink_mask, uint32_t block_payload, int32_t ref_shift,
+                   bool deflated, xm_strip_bam_bins *out)
+{
     if (!s || slot < 0 || slot >= XMS_SLOTS || !out) return XM_ERR_INVALID_ARG;
     Slot &sl = s->slot[slot];
     if (n_records > sl.record_cap || n_records > 0xFFFFFFF0ull || sl.last_score_mode < 0 || !sl.classified) return XM_ERR_INVALID_ARG;
@@ -1615,8 +1671,38 @@ int xm_strip_fetch_bins_bam(xm_strip *s, int slot, uint64_t n_records, int paire
         sl.member_cap = cnt;
     }
     const uint32_t nm = (uint32_t)n_members;
+    const uint32_t slot_bytes = (P + STORED_HEAD + 15u) & ~15u;              // what a member's stream never exceeds, rounded up to 16
+    if (deflated) XMF_TRY(ensure_bamz(s, sl, n_members, slot_bytes));
     sam_enc_write_kernel<<<(uint32_t)((lines64 + 3u) / 4u), 256, 0, st>>>(ef[0], ef[1], sl.d_idx, d_off, n_units, n, paired ? 1 : 0, sink_mask, sl.d_usize,
                                                                           sl.d_uplace, ref_shift, sl.d_pay, (uint32_t)sl.pay_cap);
+    if (deflated) {
+        // E2's payload buffer is the layout bamz_layout_kernel describes (bin b from starts[b] on, no frames): pass F is not run.  The
+        // members' streams, their CRCs, the scan of their lengths + 26, the pack; where the bins lie is known only behind the encoder.
+        // Whether the stream fits was decided above, by the stored route's sums: a deflated member is never longer than its stored
+        // form (XMB_DEFLATE_BOUND), so what the pack writes lies inside the bytes those sums count.
+        std::memset(out->bin_off, 0, sizeof out->bin_off);
+        bamz_layout_kernel<<<(nm + 255u) / 256u, 256, 0, st>>>(sl.d_gstate + GS_STARTS, P, slot_bytes, nm, sl.d_layout, sl.d_members);
+        int rcz = xm_bgzf_deflate_dev(s->ctx, st, sl.d_pay, sl.d_members, n_members, sl.d_zcomp, sl.d_zclen, sl.d_zstatus, sl.d_zwork, sl.z_work_bytes);
+        if (rcz == XM_OK) rcz = xm_bgzf_crc32_dev(s->ctx, st, sl.d_pay, sl.d_members, n_members, sl.d_member_crc);
+        if (rcz != XM_OK) { take_ctx_error(s); return rcz; }
+        bamz_place_kernel<<<1, BAMZ_PLACE_THREADS, 0, st>>>(sl.d_members, sl.d_zclen, sl.d_zstatus, nm, sl.d_layout, sl.d_zoff, sl.d_zplaced);
+        bgzf_pack_kernel<<<nm, 64, 0, st>>>(sl.d_zcomp, sl.d_members, sl.d_zclen, sl.d_member_crc, reinterpret_cast<const uint64_t *>(sl.d_zoff), nm,
+                                            sl.d_out);
+        XMF_HIP(s, hipMemcpyAsync(sl.h_zplaced, sl.d_zplaced, 9 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        XMF_TRY(wait_for(s, st, nullptr));
+        if (sl.h_zplaced[8] != 0ull || sl.h_zplaced[7] > framed) {
+            char text[160];
+            snprintf(text, sizeof text, "xm_strip_fetch_bins_bamz: members were not encoded (status bits 0x%llx: %s), %llu bytes placed of at most %llu",
+                     sl.h_zplaced[8], xm_bgzf_strerror((uint32_t)sl.h_zplaced[8]), sl.h_zplaced[7], (unsigned long long)framed);
+            std::lock_guard<std::mutex> hold(s->error_lock);
+            s->last_error = text;
+            return XM_ERR_HIP;
+        }
+        for (int k = 0; k < 8; ++k) out->bin_off[k] = sl.h_zplaced[k];
+        const int rc = Slot::send_home(s, st, sl.copy_stream, sl.ev_filled, sl.ev_out, sl.d_out, sl.h_out, sl.h_zplaced[7]);
+        sl.out_issued = true;
+        return rc;
+    }
     bam_layout_kernel<<<(nm + 255u) / 256u, 256, 0, st>>>(sl.d_gstate + GS_STARTS, P, nm, sl.d_layout, sl.d_members);
     sam_enc_frame_copy_kernel<<<nm, 256, 0, st>>>(sl.d_pay, (uint32_t)at.total, sl.d_gstate + GS_STARTS, sl.d_layout, sl.d_members, nm, P, sl.d_out,
                                                   (uint32_t)sl.out_cap);
@@ -1627,6 +1713,10 @@ int xm_strip_fetch_bins_bam(xm_strip *s, int slot, uint64_t n_records, int paire
     sl.out_issued = true;
     return rc;
 }
+
+}  // namespace
+
+extern "C" {
 
 int xm_strip_out_wait(xm_strip *s, int slot)
 {

@@ -337,19 +337,26 @@ _HEADER_PLAN = (            # sink keyword, which input's header, @CO text   (re
 
 
 def process_headers(file1, file2, primary_specific=sys.stdout, secondary_specific=None, primary_multi=None,
-                    secondary_multi=None, unassigned=None, unresolved=None, bam=False, output_format="sam"):
+                    secondary_multi=None, unassigned=None, unresolved=None, bam=False, output_format="sam", encode_sam=False):
     """Read both headers and write each open sink its header (ref :133-174).  primary_specific is
     written unconditionally; secondary bins get file2's header, the rest file1's.
-    output_format="bam" (BAM inputs only): each sink gets a BGZF-framed BAM header instead -- the same text, and the reference
-    list of the input its records come from; `unresolved` holds records of both inputs and gets both lists
-    (_merge_unresolved_header).  Nothing is written when any sink has to be refused."""
+    output_format="bam" (BAM inputs, or SAM inputs with encode_sam=True): each sink gets a BGZF-framed BAM header instead -- the same
+    text, and the reference list of the input its records come from (SAM inputs: the list its @SQ lines make, _sam_header_refs);
+    `unresolved` holds records of both inputs and gets both lists (_merge_unresolved_header).  Nothing is written when any sink has
+    to be refused."""
     if output_format not in ("sam", "bam"):
         raise ValueError("output_format must be 'sam' or 'bam'")
-    if output_format == "bam" and not bam:
+    if encode_sam and (output_format != "bam" or bam):
+        raise ValueError("encode_sam needs output_format='bam' and SAM inputs (bam=False)")
+    if output_format == "bam" and not bam and not encode_sam:
         raise ValueError("BAM outputs need BAM inputs (bam=True)")
-    if output_format == "bam":
+    if encode_sam:
+        headers = (get_sam_header(file1), get_sam_header(file2))
+        refs = tuple(_sam_header_refs(lines) for lines in headers)
+    elif output_format == "bam":
         inputs = (_bam_image(file1), _bam_image(file2))
         headers = tuple(_bam_header_lines(data) for data in inputs)
+        refs = tuple(_bam_header_of(data)[1] for data in inputs)
     else:
         reader = get_bam_header if bam else get_sam_header
         headers = (reader(file1), reader(file2))
@@ -359,7 +366,6 @@ def process_headers(file1, file2, primary_specific=sys.stdout, secondary_specifi
     if output_format == "bam":
         keys = [key for key, _which, _comment in _HEADER_PLAN]
         wrapped = dict(zip(keys, _bam_sinks([sinks[key] for key in keys])))
-        refs = tuple(_bam_header_of(data)[1] for data in inputs)
         images = {}
         for key, which, comment in _HEADER_PLAN:                     # every image is made before any is written
             if wrapped[key]:
@@ -1207,6 +1213,81 @@ def _merge_unresolved_header(header1, header2, refs1, refs2):
     return header1[:last + 1] + sq2 + header1[last + 1:], list(refs1) + list(refs2)
 
 
+def _sam_header_refs(header):
+    """The reference list the @SQ lines of a SAM header make: [(name bytes, length)] in the order of the lines (SAM specification
+    1.3: fields separated by tabs, SN and LN at any position among them).  ValueError naming the line for a missing SN or LN, an LN
+    outside 1 .. 2^31 - 1, or a name that occurs twice.  No @SQ line: an empty list (a mapped record is then refused when met)."""
+    refs, seen = [], set()
+    for line in header:
+        line = line.decode("latin-1") if isinstance(line, (bytes, bytearray)) else line
+        line = line.rstrip("\r\n")
+        fields = line.split("\t")
+        if fields[0] != "@SQ":
+            continue
+        name = length = None
+        for field in fields[1:]:
+            if field[:3] == "SN:" and name is None:
+                name = field[3:]
+            elif field[:3] == "LN:" and length is None:
+                length = field[3:]
+        if not name:
+            raise ValueError("@SQ line without SN: %r" % line)
+        if length is None:
+            raise ValueError("@SQ line without LN: %r" % line)
+        if not (length.isascii() and length.isdigit()) or not 1 <= int(length) <= 2 ** 31 - 1:
+            raise ValueError("@SQ line with an LN outside 1 .. 2^31 - 1: %r" % line)
+        name = name.encode("latin-1")
+        if name in seen:
+            raise ValueError("reference %r occurs twice: @SQ line %r" % (name.decode("latin-1"), line))
+        seen.add(name)
+        refs.append((name, int(length)))
+    return refs
+
+
+def _sam_records_of(bin_text, b, paired, names, ref_shift, paths=("file 1", "file 2")):
+    """The host encoder of one bin of SAM text as BAM records (SAM inputs, BAM outputs: the windows the device does not deliver).
+    bin_text: the bin's text exactly as the SAM route would write it (Parser.emit: '\\t'.join(fields) + '\\n' per line, in the
+    reference's order -- primary bins file 1's lines, secondary bins file 2's, `unresolved` (4) per unit file 1's line(s) and then
+    file 2's; a paired unit has two lines of each).  names: per file, its reference names; file 2's lines of bin 4 are encoded
+    against file 2's names and their reference ids moved up by ref_shift.  -> the records back to back (bytes), in the order of the
+    lines.  A line the encoder refuses: ValueError naming the file, the QNAME and the XMH_ENC_* reason."""
+    from . import _host
+    text = np.frombuffer(bin_text, dtype=np.uint8) if isinstance(bin_text, (bytes, bytearray)) else np.asarray(bin_text, dtype=np.uint8)
+    ends = np.flatnonzero(text == 10).astype(np.int64)
+    if ends.shape[0] == 0:
+        return b""
+    starts = np.concatenate(([0], ends[:-1] + 1))
+    lens = ends - starts
+    k = np.arange(ends.shape[0])
+    per = 2 if paired else 1
+    of_file = ((k % (2 * per)) // per) if b == 4 else np.full(k.shape[0], 1 if b in (1, 3) else 0)
+    sizes = np.zeros(k.shape[0], dtype=np.int64)
+    parts = {}
+    for f in (0, 1):
+        mine = np.flatnonzero(of_file == f)
+        if mine.shape[0] == 0:
+            continue
+        rec, size, bad, reason = _host.sam_encode(text, starts[mine], lens[mine], names[f], ref_shift=ref_shift if (f == 1 and b == 4) else 0)
+        if bad is not None:
+            at = int(mine[bad])
+            fields = bytes(text[starts[at]:ends[at]]).split(b"\t")
+            what = _host.SAM_ENC_REASONS.get(reason, "XMH_ENC %d" % reason)
+            if reason in (4, 8) and len(fields) > 6:
+                what += ": %s %r is not in the header" % (("RNAME", fields[2].decode("latin-1")) if reason == 4 else ("RNEXT", fields[6].decode("latin-1")))
+            raise ValueError("%s: the line of read %r cannot be written as a BAM record (%s)" % (paths[f], fields[0].decode("latin-1"), what))
+        sizes[mine] = size
+        parts[f] = (mine, np.frombuffer(rec, dtype=np.uint8), size.astype(np.int64))
+    if len(parts) == 1:
+        return bytes(next(iter(parts.values()))[1])
+    place = np.cumsum(sizes) - sizes                                 # both files' records, interleaved back by their sizes
+    out = np.empty(int(sizes.sum()), dtype=np.uint8)
+    for mine, rec, size in parts.values():
+        first = np.cumsum(size) - size
+        within = np.arange(rec.shape[0], dtype=np.int64) - np.repeat(first, size)
+        out[np.repeat(place[mine], size) + within] = rec
+    return out.tobytes()
+
+
 def _bam_records_of(seg, paired, b, raws, offs, ref_shift=0):
     """The host assembler of one bin's records: for the units `seg` (pair indices, input order) the bytes of the records the bin
     takes -- primary bins file 1's, secondary bins file 2's, `unresolved` (4) file 1's then file 2's; a paired unit is records
@@ -1697,7 +1778,7 @@ class _FileRun(object):
                 self.bamdev = default_bamdev()
             except MemoryError:
                 self.bamdev = None
-        if out_bam and self.bamdev is None:
+        if out_bam and bam and self.bamdev is None:
             raise RuntimeError("BAM outputs need the GPU BAM front end (BAM inputs, a min_score that is a number, XENOMAPPER_GPU_BAM "
                                "not 0, and memory for its buffers)")
         with self.prof("open"):
@@ -1737,7 +1818,18 @@ class _FileRun(object):
         # host threads, from the packed records; a window with floating-point fields is printed that way in any case)
         self.bam_text_on_device = False
         self.ref_shift = 0                                           # BAM outputs: file 2's reference ids in `unresolved` (its list follows file 1's)
-        if out_bam and sinks[4]:
+        self.sam_names = None                                        # SAM inputs, BAM outputs: per file, the reference names its @SQ lines give
+        if out_bam and not bam:
+            headers = [bytes(src.raw[:_record_start(src.raw)]).decode("latin-1").splitlines() for src in self.sources]
+            refs = [_sam_header_refs(lines) for lines in headers]
+            if sinks[4]:                                             # the clash rule of the header, before anything is written
+                _merge_unresolved_header(headers[0], headers[1], refs[0], refs[1])
+                self.ref_shift = len(refs[0])
+            self.sam_names = [[name for name, _len in r] for r in refs]
+            if self.stripper is not None:
+                for f in (0, 1):
+                    self.stripper.set_refs(f, self.sam_names[f])
+        if out_bam and bam and sinks[4]:
             if self.sources[0].ref_names is None:
                 raise ValueError("the reference list of %s could not be read: `unresolved` cannot be written as BAM" % path1)
             self.ref_shift = len(self.sources[0].ref_names)
@@ -1777,6 +1869,8 @@ class _FileRun(object):
             except _host.NonAsciiInput:
                 if self.bam:
                     raise ValueError("non-ASCII bytes in BAM text fields are not supported")
+                if self.out_bam:
+                    raise ValueError("non-ASCII bytes in SAM input cannot be written as BAM records")
                 return _finish_in_python(self.mode, self.paths[0], self.paths[1], [src.pos for src in self.sources], self.sinks,
                                          self.min_score, self.tag_func, self.skip_repeated, self.totals, self.key_order)
             block, eofs = win.block, win.eofs
@@ -1899,10 +1993,19 @@ class _FileRun(object):
             # with a wanted line that needs re-joining, or with more text than the buffers hold, is written as before.
             with prof("classify"):
                 win.classified = stripper.classify(which, self.mode, blk.n, _floor_min_score(self.min_score))
-                bins = stripper.fetch_bins(which, blk.n, self.paired, self.sink_mask)
+                if self.out_bam:
+                    # BAM outputs: every wanted line encoded as a BAM record on the device, framed (xm_strip_fetch_bins_bam) or deflated
+                    # and framed there (bam_compress: xm_strip_fetch_bins_bamz).  A window the device declines -- a host-only form, a
+                    # line outside the grammar, more bytes than the buffers hold -- is encoded by the host (_sam_records_of).
+                    fetch = stripper.fetch_bins_bamz if self.bam_compress else stripper.fetch_bins_bam
+                    bins = fetch(which, blk.n, self.paired, self.sink_mask, 0, self.ref_shift)[:3]
+                    key = "sam_windows_device_bamz_bins" if self.bam_compress else "sam_windows_device_bam_bins"
+                else:
+                    bins = stripper.fetch_bins(which, blk.n, self.paired, self.sink_mask)
+                    key = "sam_windows_device_bins"
             if bins[0] == 0:
                 win.bins = bins
-                prof.add("sam_windows_device_bins", 1)
+                prof.add(key, 1)
                 win.finish = self._await_sam_bins
         prof.add("sam_windows", 1)
         if blk.overflow or (self.cigar_mode and blk.n_exceptions):
@@ -2234,6 +2337,8 @@ class _FileRun(object):
     def _write_bins(self, win, parser, code, idx, off, limit, ready):
         """The units of one window to the sinks, bin by bin; `limit`: only the units in front of that index."""
         prof, paired = self.prof, self.paired
+        if self.sam_names is not None and ready is None:
+            prof.add("sam_windows_host_bam", 1)
         for b in range(6):
             sink = self.sinks[b]
             if not sink:
@@ -2244,8 +2349,8 @@ class _FileRun(object):
                 _st, text, boff = ready
                 if boff[b + 1] > boff[b]:
                     piece = text[boff[b]:boff[b + 1]]
-                    if self.out_bam:                             # what crossed the link is what is written: the framed members
-                        prof.add("bam_out_bytes", int(boff[b + 1] - boff[b]))
+                    # what crossed the link is what is written: the framed members, or the lines
+                    prof.add("bam_out_bytes" if self.out_bam else "sam_out_bytes", int(boff[b + 1] - boff[b]))
                     with prof("emit"):
                         done = _emit_into_file(parser, paired, b, None, sink, self.ahead, self.ahead_pool, ready=piece)
                     if not done:
@@ -2257,7 +2362,16 @@ class _FileRun(object):
             seg = idx[int(off[b]):int(off[b + 1])]
             if limit is not None:
                 seg = seg[seg < limit]
-            if self.out_bam:
+            if self.sam_names is not None:
+                # SAM inputs, BAM outputs, a window the device did not deliver: the bin's text as the SAM route writes it, encoded by
+                # the host (xmh_sam_encode) and framed as the BAM route's host windows are
+                with prof("emit"):
+                    text = parser.emit(paired, b, seg, reuse=True)
+                    data = _bgzf_frame(_sam_records_of(text, b, paired, self.sam_names, self.ref_shift, self.paths), 1)
+                prof.add("bam_out_bytes", len(data))
+                with prof("write"):
+                    _write_bytes(sink, data)
+            elif self.out_bam:
                 # BAM outputs of a window the device did not gather: the same records through the host assembler
                 with prof("emit"):
                     data = _bgzf_frame(_bam_records_of(seg, paired, b, win.bam_src[0], win.bam_src[1], self.ref_shift), 1)
@@ -2367,7 +2481,7 @@ def _finish_in_python(mode, path1, path2, pos, sinks, min_score, tag_func, skip_
 def classify_sam_files(primary_sam, secondary_sam, primary_specific=sys.stdout, secondary_specific=None,
                        primary_multi=None, secondary_multi=None, unassigned=None, unresolved=None, paired=False,
                        conservative=False, min_score=float("-inf"), tag_func=get_tag, skip_repeated_reads=None,
-                       n_threads=0, bam=False, output_format="sam", bam_compress=False):
+                       n_threads=0, bam=False, output_format="sam", bam_compress=False, encode_sam=False):
     """File-level entry point: classify two SAM files (paths) whose headers the caller has already dealt with
     (process_headers).  Equivalent to main_*(getReadPairs(open(primary_sam), open(secondary_sam), ...)) after the
     header lines, but parses and writes through the C++ stripper.  tag_func must be one of the three built-in
@@ -2380,9 +2494,16 @@ def classify_sam_files(primary_sam, secondary_sam, primary_specific=sys.stdout, 
     (TypeError), no GPU BAM front end (RuntimeError).
     bam_compress=True (output_format="bam" only, else ValueError): ordinary compressed BAM -- every member deflated on the GPU
     (xm_bamdev_fetch_bins_bamz: one dynamic-Huffman block, or a stored one where that is not shorter); windows the host assembles
-    are deflated by zlib at level 1, as they are without it.  Default False: the stored members, byte for byte as before."""
+    are deflated by zlib at level 1, as they are without it.  Default False: the stored members, byte for byte as before.
+    encode_sam=True (output_format="bam" and bam=False only, else ValueError): SAM inputs, BAM outputs -- every line of a unit
+    encoded as the BAM alignment record htslib's SAM parser makes of it, on the GPU (xm_strip_fetch_bins_bam; with bam_compress
+    xm_strip_fetch_bins_bamz), against the reference list of the file's @SQ lines; a window the device declines is encoded by the
+    host (xmh_sam_encode).  A line neither takes -- an RNAME that is not in the header, a line outside the grammar -- and non-ASCII
+    input raise ValueError, and the outputs are left without their end-of-file marker."""
     if output_format not in ("sam", "bam"):
         raise ValueError("output_format must be 'sam' or 'bam'")
+    if encode_sam and (output_format != "bam" or bam):
+        raise ValueError("encode_sam needs output_format='bam' and SAM inputs (bam=False)")
     if bam_compress and output_format != "bam":
         raise ValueError("bam_compress needs output_format='bam'")
     if tag_func not in (get_tag, get_tag_with_ZS_as_XS, get_cigarbased_AS_tag):
@@ -2392,7 +2513,7 @@ def classify_sam_files(primary_sam, secondary_sam, primary_specific=sys.stdout, 
     mode = _ffi.MODE_SE if not paired else (_ffi.MODE_PE_CONSERVATIVE if conservative else _ffi.MODE_PE_LIBERAL)
     sinks = _sinks(primary_specific, secondary_specific, primary_multi, secondary_multi, unassigned, unresolved)
     if output_format == "bam":
-        if not bam:
+        if not bam and not encode_sam:
             raise ValueError("BAM outputs need BAM inputs (bam=True)")
         sinks = _bam_sinks(sinks)
         counts = _run_files(mode, primary_sam, secondary_sam, sinks, min_score, tag_func, skip_repeated_reads, n_threads, bam,
@@ -2514,6 +2635,7 @@ def command_line_interface(*args, **kw):
     # (not in --help: its text is the reference's, byte for byte; README documents the flag)
     parser.add_argument("--bam_outputs", action="store_true", help=argparse.SUPPRESS)
     parser.add_argument("--bam_compress", action="store_true", help=argparse.SUPPRESS)
+    parser.add_argument("--encode_sam", action="store_true", help=argparse.SUPPRESS)
     ns = parser.parse_args(*args, **kw)
     if ns.version:
         print(__version__)
@@ -2522,8 +2644,12 @@ def command_line_interface(*args, **kw):
         print("ERROR: You must provide --primary_sam and --secondary_sam\n or --primary_bam and --secondary_bam\n")
         parser.print_help()
         sys.exit(1)
-    if ns.bam_outputs and (not ns.primary_bam or not ns.secondary_bam):
-        parser.error("--bam_outputs needs --primary_bam and --secondary_bam")
+    if ns.encode_sam and not ns.bam_outputs:
+        parser.error("--encode_sam needs --bam_outputs")
+    if ns.encode_sam and (ns.primary_bam or ns.secondary_bam or not ns.primary_sam or not ns.secondary_sam):
+        parser.error("--encode_sam needs --primary_sam and --secondary_sam, and no BAM inputs")
+    if ns.bam_outputs and not ns.encode_sam and (not ns.primary_bam or not ns.secondary_bam):
+        parser.error("--bam_outputs needs --primary_bam and --secondary_bam (or --encode_sam with SAM inputs)")
     if ns.bam_compress and not ns.bam_outputs:
         parser.error("--bam_compress needs --bam_outputs")
     return ns
@@ -2541,6 +2667,18 @@ def main(argv=None):
                  primary_multi=args.primary_multi, secondary_multi=args.secondary_multi,
                  unassigned=args.unassigned, unresolved=args.unresolved)
     skip_repeated = not args.paired
+    if args.bam_outputs and args.encode_sam:
+        # SAM in, BAM out: the lines encoded as BAM records on the GPU, through the handles' binary buffers
+        process_headers(args.primary_sam, args.secondary_sam, output_format="bam", encode_sam=True, **sinks)
+        category_counts = classify_sam_files(args.primary_sam.name, args.secondary_sam.name, paired=args.paired,
+                                             conservative=args.conservative, min_score=args.min_score, tag_func=tag_func,
+                                             skip_repeated_reads=skip_repeated, output_format="bam", encode_sam=True,
+                                             bam_compress=args.bam_compress, **sinks)
+        output_summary(category_counts=category_counts, outfile=sys.stderr)
+        for sink in sinks.values():
+            if sink:
+                sink.flush()
+        return
     if args.bam_outputs:
         # BAM in, BAM out: the records as they stand, framed on the GPU, through the handles' binary buffers
         process_headers(args.primary_bam, args.secondary_bam, bam=True, output_format="bam", **sinks)
