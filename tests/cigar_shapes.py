@@ -11,7 +11,7 @@ per workgroup) or a wave (K1c: 256 records, 4 waves per workgroup) on every valu
             from small per-record counts and once from a few records of 254 ops
   records   records of 0, 3, 4, 254, 255, 256, 511, 512, 513 ops; escaped records (255 ops or more) at the last record of a
             tile, in front of a workgroup, at record n - 1
-  end       the last full tile 9, 8, 7, 0 ops in front of the end of the op array; n a multiple of 2048; K1c's last chunk
+  end       the last full tile 9, 8, 7, 6, 0 ops in front of the end of the op array; n a multiple of 2048; K1c's last chunk
             ending at, one below and one above the end of the array; a partial workgroup whose last record begins within
             three words of the end
   oplen     ops of length 2^20 - 1 and 2^20 (own and only over-read from the next tile), 2^24, 2^28 - 1; the largest table
@@ -43,7 +43,7 @@ OP_CHARS = "MIDNSHP=X"
 
 STRETCHES = (0, 1, 255, 256, 257, 511, 512, 513, 767, 768, 769) + tuple(range(1020, 1028))
 RECORD_OPS = (0, 3, 4, 254, 255, 256, 511, 512, 513)
-END_DISTANCES = (9, 8, 7, 0)
+END_DISTANCES = (9, 8, 7, 6, 0)             # 6: as far as K1p's widest load reaches past a stretch (W = 8 k + 1: words te .. te + 6)
 SIZES = (1, 3, 4, 5, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049)
 K1P_CLASSES = ("brief", "one_chunk", "two_chunks", "slow_W", "slow_end", "slow_escape", "slow_long_op", "slow_counts",
                "slow_big", "partial")

@@ -1,6 +1,7 @@
 // Stand-in for <hip/hip_runtime.h>: with this directory first on the include path and XM_LOCKSTEP_HOST defined,
 // xenomapper_amd/csrc/xm_kernels.hip compiles as plain C++ (ROCm's host clang++, -x c++) and its kernels execute on the CPU,
-// lane by lane, where ASan and UBSan can watch them (tests/lockstep_place_host.cpp, tests/test_lockstep_place_cpu.py).
+// lane by lane, where ASan and UBSan can watch them (tests/lockstep_place_host.cpp, tests/test_lockstep_place_cpu.py: the fused
+// step's launches; tests/lockstep_kernels_host.cpp, tests/test_lockstep_kernels_cpu.py: every other launcher of the file).
 //
 // How a launch executes (lockstep.h has the runtime):
 //   - workgroups run one after another; the waves of a workgroup run concurrently, one host thread each;
@@ -13,6 +14,16 @@
 //     operations end the program with a message naming both lines; a wave that makes no progress for some seconds (a lane in
 //     an endless loop, a wave waiting at a barrier the others never reach) ends it through the watchdog.  Lanes that have
 //     returned take no part: a ballot sees them as 0, reading one of them is an error;
+//   - a cross-lane operation that only part of the running lanes reach is therefore an error -- also where HIP allows it (a
+//     ballot inside a divergent branch is a ballot over the lanes in that branch) -- unless the kernel source declares the
+//     subset: `XM_IF_LANES(cond) statement [else statement]` (xm_kernels.hip; a plain `if` on the device).  All lanes running
+//     together meet at the marker with their cond.  Those with cond true run the statement as a wave of their own until each
+//     has reached its end or returned: a ballot sees them only (the other lanes' bits are 0), __shfl_xor, readlane,
+//     ds_bpermute and update_dpp from a lane outside the subset end the program as reading a returned lane does, and so
+//     does a __syncthreads inside the statement.  Then the lanes with cond false run the else branch the same way, and
+//     everybody goes on together.  A marker inside a marked statement ends the program: nothing needs it yet.  The rule for
+//     unmarked code is as strict as before.  lockstep.h defines LS_SUBSETS to say that it models this: xm_kernels.hip opens the
+//     scope only then, so it still compiles against a shim that does not;
 //   - __shared__ is a static in the section xm_lds: one copy serves the workgroup.  The runtime fills the section
 //     from __start_xm_lds to __stop_xm_lds with the byte of ls::set_fill() before every workgroup, so that a kernel which
 //     reads LDS it has not written gives results that depend on the fill.  ASan puts no redzones between globals of a

@@ -26,6 +26,8 @@
 #endif
 #endif
 
+#define LS_SUBSETS 1             // this shim models declared subsets of a wave (ls::Subset, XM_IF_LANES of xm_kernels.hip)
+
 extern "C" char __start_xm_lds[], __stop_xm_lds[];
 
 namespace ls {
@@ -35,11 +37,11 @@ struct dim3 {
     dim3(uint32_t x_ = 1, uint32_t y_ = 1, uint32_t z_ = 1) : x(x_), y(y_), z(z_) {}
 };
 
-enum Op { OP_NONE, OP_BALLOT, OP_SHFL, OP_READLANE, OP_READFIRST, OP_DPP, OP_BPERM, OP_SETTLE, OP_SYNC };
+enum Op { OP_NONE, OP_BALLOT, OP_SHFL, OP_READLANE, OP_READFIRST, OP_DPP, OP_BPERM, OP_SETTLE, OP_SYNC, OP_ENTER, OP_LEAVE };
 inline const char *op_name(int op)
 {
     static const char *names[] = {"none", "__ballot", "__shfl_xor", "readlane", "readfirstlane", "update_dpp", "ds_bpermute",
-                                  "lds_settle", "__syncthreads"};
+                                  "lds_settle", "__syncthreads", "XM_IF_LANES", "the end of XM_IF_LANES"};
     return names[op];
 }
 
@@ -68,6 +70,10 @@ struct Wave {
     int n_lanes;
     uint64_t snap[WAVE];          // the values of the rendezvous being resumed from
     bool snap_live[WAVE];
+    // a declared subset (XM_IF_LANES): scope 0 = none, 1 = the lanes whose condition held run the marked statement,
+    // 2 = the others run its else branch.  `active` lanes are scheduled; the others wait at the marker or at its end.
+    int scope, scope_line;
+    bool active[WAVE], member[WAVE], taken[WAVE];
     jmp_buf sched;
     const void *sched_bottom;
     size_t sched_size;
@@ -191,28 +197,62 @@ inline void run_wave(Wave *w)
         l->op = OP_NONE;
         l->fake = nullptr;
     }
+    w->scope = 0;
+    for (int i = 0; i < WAVE; ++i) w->active[i] = i < w->n_lanes;
     for (;;) {
         int first = -1;
         for (int i = 0; i < w->n_lanes; ++i) {
             Lane *l = &w->lane[i];
-            if (!l->live) continue;
+            if (!l->live || !w->active[i]) continue;
             to_lane(w, l);
             if (!l->live) continue;
+            if (l->op == OP_LEAVE) {                           // done with its branch of a declared subset: waits for the others
+                if (w->scope == 0 || l->line != w->scope_line)
+                    die("wave %d: lane %d leaves the XM_IF_LANES of line %d, which the wave has not entered", w->index, i, l->line);
+                w->active[i] = false;
+                continue;
+            }
             if (first < 0) first = i;
             else if (l->op != w->lane[first].op || l->line != w->lane[first].line)
                 die("divergence in wave %d: lane %d is at %s of line %d, lane %d at %s of line %d", w->index, first,
                     op_name(w->lane[first].op), w->lane[first].line, i, op_name(l->op), l->line);
         }
         g_progress.fetch_add(1, std::memory_order_relaxed);
-        if (first < 0) break;                                  // every lane has returned
+        if (first < 0) {
+            if (w->scope == 1) {                               // the marked statement is done: now the else branch's lanes
+                w->scope = 2;
+                for (int i = 0; i < WAVE; ++i) w->active[i] = w->member[i] && !w->taken[i];
+                continue;
+            }
+            if (w->scope == 2) {                               // everybody goes on together
+                w->scope = 0;
+                for (int i = 0; i < WAVE; ++i) w->active[i] = w->member[i];
+                continue;
+            }
+            break;                                             // every lane has returned
+        }
+        const int op = w->lane[first].op, line = w->lane[first].line;
         for (int i = 0; i < WAVE; ++i) {
-            const bool live = i < w->n_lanes && w->lane[i].live;
+            const bool live = i < w->n_lanes && w->lane[i].live && w->active[i];
             w->snap_live[i] = live;
             w->snap[i] = live ? w->lane[i].dep : 0;
         }
-        w->at_op = w->lane[first].op;
-        w->at_line = w->lane[first].line;
-        if (w->lane[first].op == OP_SYNC) g_barrier.arrive_and_wait(w->index, w->lane[first].line);
+        w->at_op = op;
+        w->at_line = line;
+        if (op == OP_ENTER) {
+            if (w->scope != 0) die("wave %d: XM_IF_LANES of line %d inside the XM_IF_LANES of line %d: nested subsets are not modelled", w->index, line, w->scope_line);
+            w->scope = 1;
+            w->scope_line = line;
+            for (int i = 0; i < WAVE; ++i) {
+                w->member[i] = w->snap_live[i];
+                w->taken[i] = w->snap_live[i] && (w->snap[i] & 1u) != 0u;
+                w->active[i] = w->taken[i];
+            }
+        }
+        if (op == OP_SYNC) {
+            if (w->scope != 0) die("wave %d: __syncthreads of line %d inside the XM_IF_LANES of line %d", w->index, line, w->scope_line);
+            g_barrier.arrive_and_wait(w->index, line);
+        }
     }
     g_barrier.drop();
 }
@@ -299,12 +339,25 @@ inline T from_bits(uint64_t b)
 inline uint64_t value_of(int lane, const char *what, int line)
 {
     const Wave *w = cur->wave;
-    if (lane < 0 || lane >= WAVE || !w->snap_live[lane]) die("%s of line %d: lane %d reads lane %d, which is not running", what, line, cur->id, lane);
+    if (lane < 0 || lane >= WAVE || !w->snap_live[lane])
+        die("%s of line %d: lane %d reads lane %d, which is not running%s", what, line, cur->id, lane,
+            w->scope != 0 ? " in this branch of XM_IF_LANES" : "");
     return w->snap[lane];
 }
 
 inline void syncthreads(int line) { rendezvous(OP_SYNC, line, 0); }
 inline void settle(int line) { rendezvous(OP_SETTLE, line, 0); }
+
+// XM_IF_LANES(cond): the lanes running together meet here with their cond; those with cond true then run the marked
+// statement as a wave of their own (a ballot sees only them, reading another lane is an error, __syncthreads is one) until
+// each has reached the statement's end or returned, then the others run the else branch the same way (run_wave)
+struct Subset {
+    bool taken;
+    int line;
+    Subset(bool cond, int line_) : taken(cond), line(line_) { rendezvous(OP_ENTER, line, cond ? 1u : 0u); }
+    ~Subset() { rendezvous(OP_LEAVE, line, 0); }
+    Subset(const Subset &) = delete;
+};
 
 inline uint64_t ballot(bool p, int line)
 {
@@ -364,6 +417,8 @@ inline int update_dpp(int old, int src, int ctrl, int row_mask, int bank_mask, b
     } else {
         die("update_dpp of line %d: control 0x%x with row mask 0x%x is not modelled", line, ctrl, row_mask);
     }
+    if (from >= 0 && w->scope != 0 && w->member[from] && w->lane[from].live && !w->snap_live[from])
+        die("update_dpp of line %d: lane %d reads lane %d, which is not running in this branch of XM_IF_LANES", line, lane, from);
     if (from < 0 || !w->snap_live[from]) return old;
     return from_bits<int>(w->snap[from]);
 }

@@ -9,7 +9,6 @@ Sizes: 1, 2047, 2048, 2049 (one or two granules: every destination, both scatter
 XM_SCATTER_WAVES 7 and 100 give runs of 6 granules with a short last run, and one granule per wave), 2 097 157 (1024 granules + 5:
 the scan's part carry) and 4 196 357 (2049 granules + 5: the chunked order of place_steps at XM_PLACE_CHUNK_PARTS=1)."""
 import os
-import shutil
 import struct
 import subprocess
 
@@ -17,10 +16,11 @@ import numpy as np
 import pytest
 
 from tests import helpers as H
+from tests import lockstep_build as L
 from tests import runs_shapes as S
 
 GRAN = 2048
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+ENV = L.ENV
 ABSENT = -2**31
 IN_BINS4, IN_CODE, IN_HIST = 0, 1, 2
 TO_FLAT, TO_LISTS, TO_LISTS_STATE6 = 0, 1, 2
@@ -31,31 +31,9 @@ CHUNKED_N = 2049 * GRAN + 5
 MASKS = ("interleaved", "pe2_p55", "se_all", "pe1_p30", "se_staged_then_not", "skew85")
 
 
-def host_clangxx():
-    """ROCm's host clang++ (g++ has no ext_vector_type), found from hipcc as xenomapper_amd/build.py finds that."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    roots = [os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))] if os.path.exists(hipcc) else []
-    roots += [os.environ.get("ROCM_PATH", ""), "/opt/rocm"]
-    for root in roots:
-        for rel in ("llvm/bin/clang++", "lib/llvm/bin/clang++"):
-            exe = os.path.join(root, rel)
-            if root and os.path.exists(exe):
-                return exe
-    return None
-
-
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    cxx = host_clangxx()
-    if cxx is None:
-        pytest.skip("ROCm's host clang++ not found: the lockstep build of xm_kernels.hip needs it")
-    path = str(tmp_path_factory.mktemp("lockstep") / "lockstep_place_host")
-    # use-after-return detection off: it gives every lane context a fake stack of its own, mapped and unmapped per workgroup
-    subprocess.check_call([cxx, "-x", "c++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-fsanitize-address-use-after-return=never", "-Wall", "-Wextra", "-Wno-pass-failed",
-                           "-I", os.path.join(H.REPO, "tests", "lockstep"),
-                           os.path.join(H.REPO, "tests", "lockstep_place_host.cpp"), "-o", path, "-lpthread"])
-    return path
+    return L.host_program(tmp_path_factory, "lockstep_place_host")
 
 
 def random_columns(rng, n, spread=8):

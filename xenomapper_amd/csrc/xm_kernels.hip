@@ -160,6 +160,17 @@ __device__ __forceinline__ void lds_settle()
 #define XM_LAUNCH(kernel, grid, block, st, ...) kernel<<<grid, block, 0, st>>>(__VA_ARGS__)
 #endif
 
+// `XM_IF_LANES(cond) statement [else statement]`: a plain `if` whose branches hold cross-lane operations that only the lanes
+// taking the branch meet (a ballot over the running lanes is legal HIP).  The marker changes nothing on the device; to the
+// host build it declares the subset, which runs the branch as a wave of its own (tests/lockstep/hip/hip_runtime.h) -- a
+// partial-wave cross-lane operation in unmarked code stays an error there.  (LS_SUBSETS: the shim in use models subsets; with one
+// that does not the marker is the plain `if`, and such a branch ends its run with the divergence message.)
+#if defined(XM_LOCKSTEP_HOST) && defined(LS_SUBSETS)
+#define XM_IF_LANES(cond) if (ls::Subset xm_lanes_{static_cast<bool>(cond), __builtin_LINE()}; xm_lanes_.taken)
+#else
+#define XM_IF_LANES(cond) if (cond)
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // Counting (category_counts + the per-granule bin counts the stable split needs), shared by K1 (fused: the
 // category bytes are still in registers) and K2a (stand-alone compaction of category bytes from memory).
@@ -1209,11 +1220,16 @@ __device__ __forceinline__ void classify_runs_body(const T *__restrict__ as1, co
     const uint32_t incl8 = wave_scan_incl(t8);
     const uint32_t where = incl8 - t8 + off;                             // lane b < 8: this wave's run of bin b in the slab
     const uint32_t units = lane_value(incl8, 7);
+    // read by every lane, outside the selects below: lane b's `where` is taken from lane b whether or not lane b holds a
+    // unit of bin b (inside the select the read would run in the lanes of bin b only, and lane b is usually not one of them)
+    uint32_t where_b[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) where_b[b] = lane_value(where, b);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         uint32_t at = 0;
 #pragma unroll
-        for (int b = 0; b < NB; ++b) at = (bin[j] == (uint32_t)b) ? lane_value(where, b) : at;
+        for (int b = 0; b < NB; ++b) at = (bin[j] == (uint32_t)b) ? where_b[b] : at;
         if (bin[j] < 7u) slab[at + pos[j]] = (uint16_t)(threadIdx.x * 4u + (uint32_t)j);
     }
     __syncthreads();                                                     // the slab and the histogram are complete
@@ -1533,7 +1549,7 @@ __device__ __forceinline__ void classify_cigar_body(
     if (FULL || r0 < n) mb = (uint32_t)(unit_bits8[g >> 1] >> ((g & 1u) * 4u)) & 0xFu;
     if (!FULL && r0 + 4 > n) mb &= (r0 < n) ? ((1u << (uint32_t)(n - r0)) - 1u) : 0u;
     bool bad = false;
-    if (FULL || r0 < n) {
+    XM_IF_LANES(FULL || r0 < n) {                                       // a ragged workgroup: the lanes behind n skip the ballots inside
         // two dependent memory latencies in total: offsets of both species first, then the ops of both
         int32_t nmv1[4], nmv2[4];
         uint32_t o1[5], o2[5], v1[4][XM_CIG_SPEC], v2[4][XM_CIG_SPEC];
