@@ -183,6 +183,15 @@ def lib():
         "xm_bamdev_columns": ([P, I, U64, P, P, P, P, P], I),
         "xm_bamdev_cigar_columns": ([P, I, I, U64, P, P, P, P, U64, ctypes.POINTER(ctypes.c_uint64)], I),
         "xm_bamdev_last_error": ([P], ctypes.c_char_p),
+        # include/xenomapper_mappability.h
+        "xmm_abi_version": ([], I),
+        "xm_mapp_create": ([P, I, ctypes.POINTER(P)], I),
+        "xm_mapp_destroy": ([P], I),
+        "xm_mapp_reserve": ([P, I, U64, U64, U64], I),
+        "xm_mapp_staging": ([P, I], P),
+        "xm_mapp_upload": ([P, I, U64, U64], I),
+        "xm_mapp_run": ([P, I, U64, I, P, ctypes.c_uint32, I, ctypes.c_uint32, P], I),
+        "xm_mapp_last_error": ([P], ctypes.c_char_p),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -208,6 +217,11 @@ EXPORTED = ("xm_abi_version", "xm_strerror", "xm_last_hip_error", "xm_ctx_create
             "xm_bgzf_deflate_work_bytes", "xm_bgzf_deflate_dev", "xm_bgzf_compress",
             "xm_bamdev_create", "xm_bamdev_destroy", "xm_bamdev_reserve", "xm_bamdev_staging", "xm_bamdev_run", "xm_bamdev_raw_wait", "xm_bamdev_fetch_raw", "xm_bamdev_raw", "xm_bamdev_fetch_wanted", "xm_bamdev_fetch_text", "xm_bamdev_fetch_bins", "xm_bamdev_fetch_bins_bam", "xm_bamdev_fetch_bins_bamz", "xm_bamdev_set_refs", "xm_bamdev_upload", "xm_bamdev_classify",
             "xm_bamdev_columns", "xm_bamdev_cigar_columns", "xm_bamdev_last_error")
+
+
+# include/xenomapper_mappability.h, kept apart from EXPORTED (which is held equal to what three other headers declare)
+EXPORTED_MAPP = ("xmm_abi_version", "xm_mapp_create", "xm_mapp_destroy", "xm_mapp_reserve", "xm_mapp_staging", "xm_mapp_upload",
+                 "xm_mapp_run", "xm_mapp_last_error")
 
 
 def _np_ptr(a):
@@ -1261,3 +1275,63 @@ class BamDev(_FrontEnd):
 
     def raw_wait(self, slot):
         self._check(self._L.xm_bamdev_raw_wait(self._h, int(slot)), "xm_bamdev_raw_wait")
+
+
+# ---- include/xenomapper_mappability.h ----------------------------------------------------------------------------------------------
+MAPP_SLOTS = 2
+MAPP_MAX_WINDOW = 0xFFFF0000
+MAPP_OK, MAPP_DECLINED, MAPP_TOO_MANY_LINES, MAPP_TOO_MANY_VALUES = 0, 1, 2, 3
+MAPP_REASONS = ("none", "non_ascii", "separator", "fields", "name_number", "pos_number", "not_sequential")
+MAPP_SEGMENT = np.dtype([("first_line", "<u4"), ("n_lines", "<u4"), ("key_off", "<u4"), ("key_len", "<u4"), ("starts", "<u4"),
+                         ("base", "<u4"), ("last_pos", "<u4"), ("reserved", "<u4"), ("value_off", "<u8"), ("n_values", "<u8")])
+
+
+class _MappBlock(ctypes.Structure):           # xm_mapp_block
+    _fields_ = [("consumed", ctypes.c_uint64), ("n_lines", ctypes.c_uint64), ("n_segments", ctypes.c_uint64), ("n_values", ctypes.c_uint64),
+                ("status", ctypes.c_int32), ("reason", ctypes.c_int32), ("declined_line", ctypes.c_uint64),
+                ("segments", ctypes.c_void_p), ("values", ctypes.c_void_p),
+                ("carry_position", ctypes.c_uint32), ("carry_settled", ctypes.c_int32),
+                ("ms_upload", ctypes.c_float), ("ms_kernels", ctypes.c_float)]
+
+
+class MappBlock(object):
+    """One window run on the GPU (xm_mapp_block): the segment table as a MAPP_SEGMENT array and the values as uint8, both views
+    of the front end's page-locked buffers (valid until the slot is run again)."""
+
+    def __init__(self, raw):
+        for name in ("consumed", "n_lines", "n_segments", "n_values", "status", "reason", "declined_line", "carry_position"):
+            setattr(self, name, int(getattr(raw, name)))
+        self.carry_settled = bool(raw.carry_settled)
+        self.ms_upload, self.ms_kernels = float(raw.ms_upload), float(raw.ms_kernels)
+        self.segments = _host_view(raw.segments, self.n_segments, MAPP_SEGMENT)
+        self.values = _host_view(raw.values, self.n_values, np.uint8)
+
+
+class Mappability(_FrontEnd):
+    """xm_mapp: windows of name-sorted SAM text in a page-locked staging buffer -> segments and 0/1 values of the single-end
+    mappability tracks."""
+    _PREFIX, _NO_CAP = "xm_mapp_", 0
+
+    def reserve(self, slot, window_bytes, max_lines, max_values):
+        """The slot's buffers grow to these sizes; max_lines and max_values are the limits of the runs that follow."""
+        rc = self._L.xm_mapp_reserve(self._h, slot, int(window_bytes), int(max_lines), int(max_values))
+        if rc != XM_OK and 0 <= slot < MAPP_SLOTS:
+            self._cap[slot] = 0                  # a failed growth leaves the slot without buffers
+        self._check(rc, "xm_mapp_reserve")
+        self._cap[slot] = int(window_bytes)
+
+    def staging(self, slot):
+        """The slot's page-locked text buffer as a uint8 array (as long as the last reserve asked for)."""
+        return _host_view(self._L.xm_mapp_staging(self._h, slot), self._cap[slot], np.uint8)
+
+    def upload(self, slot, offset, n):
+        self._check(self._L.xm_mapp_upload(self._h, slot, int(offset), int(n)), "xm_mapp_upload")
+
+    def run(self, slot, length, eof, carry_key=None, carry_position=0):
+        """carry_key: the bytes of the key the loop holds (None: it holds none yet), carry_position: its position."""
+        raw = _MappBlock()
+        key = bytes(carry_key) if carry_key is not None else b""
+        rc = self._L.xm_mapp_run(self._h, slot, int(length), int(bool(eof)), key, len(key), int(carry_key is not None),
+                                 int(carry_position), ctypes.byref(raw))
+        self._check(rc, "xm_mapp_run")
+        return MappBlock(raw)

@@ -15,7 +15,7 @@ CSRC = os.path.join(PKG, "csrc")
 HIP_LIB = os.path.join(PKG, "libxenomapper_hip.so")
 HOST_LIB = os.path.join(PKG, "libxenomapper_host.so")
 
-HIP_SOURCES = ["xm_kernels.hip", "xm_api.hip", "xm_strip.hip", "xm_inflate.hip", "xm_deflate.hip", "xm_bamdev.hip"]
+HIP_SOURCES = ["xm_kernels.hip", "xm_api.hip", "xm_strip.hip", "xm_inflate.hip", "xm_deflate.hip", "xm_bamdev.hip", "xm_mapp.hip"]
 HOST_SOURCES = ["xm_sam.cpp", "xm_bam.cpp", "xm_samenc.cpp"]
 
 
@@ -37,9 +37,9 @@ def build_hip(force=False, verbose=False):
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
     deps = srcs + [os.path.join(CSRC, "xm_kernels.h"), os.path.join(CSRC, "xm_inflate_core.h"), os.path.join(CSRC, "xm_deflate_core.h"), os.path.join(CSRC, "xm_bgzf_pack.h"),
                    os.path.join(CSRC, "xm_bamrec.h"), os.path.join(CSRC, "xm_fmtg.h"), os.path.join(CSRC, "xm_pinned.h"), os.path.join(CSRC, "xm_gather.h"), os.path.join(CSRC, "xm_slot.h"),
-                   os.path.join(CSRC, "xm_samrec.h"), os.path.join(CSRC, "xm_bamframe.h"), os.path.join(CSRC, "xm_bamz.h"),
+                   os.path.join(CSRC, "xm_samrec.h"), os.path.join(CSRC, "xm_bamframe.h"), os.path.join(CSRC, "xm_bamz.h"), os.path.join(CSRC, "xm_mapp_kernels.h"),
                    os.path.join(REPO, "include", "xenomapper_hip.h"), os.path.join(REPO, "include", "xenomapper_strip.h"),
-                   os.path.join(REPO, "include", "xenomapper_bgzf.h")]
+                   os.path.join(REPO, "include", "xenomapper_bgzf.h"), os.path.join(REPO, "include", "xenomapper_mappability.h")]
     if not force and not _stale(HIP_LIB, deps):
         return HIP_LIB
     # XENOMAPPER_HIPCC_FLAGS: extra flags for tuning builds (e.g. -DXM_CIGAR_BLOCK=256); not used by the tests

@@ -121,6 +121,8 @@ def release_buffers():
         _stripper.close()
         _stripper = None
     _BAM_TEXT_BUFFERS.clear()
+    from . import mappability                  # (imports this module: looked up here)
+    mappability.release_front_end()            # single_end_mappability_from_sam(on_device=True)'s front end
     return _ffi.pinned_bytes()
 
 
